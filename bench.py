@@ -13,11 +13,22 @@ N` spawns the N rank processes itself (before anything touches the GPU) and rela
 0's line.  Timing: barrier + synchronize on both sides of exactly K steps, MAX over ranks;
 value = all ranks' samples / that time.
 
-Also reported (rank 0, N=1 only unless --cpu-baseline force):
-  roofline      algorithmic bytes per launch (10 B / input sample) / the
-                kernel's average HIP-event-timed duration, vs 8 TB/s HBM3E;
-  cpu_baseline  the oracle (C restatement of Fir::apply + Decimate, 1 core) on a bounded
-                sample of the same workload.
+A plain run sets up, warms up, times the K steps and prints the line; its `roofline` entry
+comes from the timed steps themselves (algorithmic bytes per launch, 10 B / input sample,
+SURVEY.md 8d, / the kernel's average HIP-event-timed duration, vs 8 TB/s HBM3E).
+
+--dump-outputs DIR writes, after the timed steps, what the last step left in the output
+buffer as DIR/y.npy (DIR/y_rank<r>.npy with more than one rank): float32 [m, 2] = (re, im).
+An output of up to 2^22 samples is written whole; of a longer one the first and the last
+4096-sample block (the first holds the FIR state carried in from the step before) and 1022
+blocks at fixed seeded offsets (dump_blocks), 32 MiB in all.  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+
+--full adds the legs that take runs of their own (rank 0 reports them in the same line):
+  channel_sharded  the configs[4] FIR bank sharded over the ranks (channel_sharded_leg);
+  cpu_baseline     the oracle (C restatement of Fir::apply + Decimate, 1 core) on a bounded
+                   sample of the same workload (N=1 only).
+--no-channel-sharded / --no-cpu-baseline drop one of them from a --full run.
 """
 from __future__ import annotations
 
@@ -52,6 +63,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--log2n", type=int, default=28, help="input samples per GPU per step")
     ap.add_argument("--algo", default="auto", choices=["auto", "direct", "os", "mx"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the channel-sharded configs[4] leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (a fixed sample) as DIR/*.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pmc-json", default=os.path.join(ROOT, "profiles", "pmc_fir_c2.json"))
@@ -456,6 +471,34 @@ def timed_region(step, steps, warmup, sync, dist=None, on_step=None):
     return elapsed
 
 
+DUMP_BLOCK = 4096      # samples per dumped block
+DUMP_NBLOCKS = 1024    # blocks dumped of an output too long to write whole (32 MiB as f32 pairs)
+DUMP_SEED = 20240
+
+
+def dump_blocks(n_out, block=DUMP_BLOCK, nblocks=DUMP_NBLOCKS, seed=DUMP_SEED):
+    """[(start, count)] of the output samples --dump-outputs writes, ascending and disjoint:
+    everything when n_out <= block * nblocks, else the first block, the last block and
+    nblocks - 2 others whose block numbers are drawn once from a seeded generator.  Pure host
+    logic, the same for every run with the same n_out (tests/test_bench_cpu.py)."""
+    if n_out <= block * nblocks:
+        return [(0, n_out)] if n_out else []
+    last = (n_out - 1) // block          # the last block may be a short one
+    pick = np.random.default_rng(seed).choice(np.arange(1, last), nblocks - 2, replace=False)
+    return [(int(b) * block, min(block, n_out - int(b) * block))
+            for b in [0] + sorted(pick.tolist()) + [last]]
+
+
+def dump_outputs(path, y, n_out, rank, world):
+    """Write this rank's sample (dump_blocks) of the n_out c64 outputs in device buffer `y` as
+    float32 [m, 2] = (re, im) to path/y.npy, or path/y_rank<r>.npy when there are more ranks."""
+    os.makedirs(path, exist_ok=True)
+    parts = [y.download(cnt, offset_bytes=8 * start) for start, cnt in dump_blocks(n_out)]
+    got = np.concatenate(parts) if parts else np.empty(0, np.complex64)
+    name = "y.npy" if world == 1 else f"y_rank{rank}.npy"
+    np.save(os.path.join(path, name), np.ascontiguousarray(got).view(np.float32).reshape(-1, 2))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -526,11 +569,14 @@ def main():
     kern_ms = float(np.mean([s.elapsed_ms(e) for s, e in zip(starts, ends)]))
     total_samples = n * args.steps * world
     value = total_samples / elapsed / 1e6
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, n_out, rank, world)
     if rank == 0:
         traffic, traffic_src = pmc_traffic(args.pmc_json, args.log2n, args.algo)
         res = headline_record(value, world, args.steps, args.warmup, elapsed, n, D, kern_ms,
                               traffic, traffic_src, args.algo)
-    if not args.no_channel_sharded:
+    channel_sharded = args.full and not args.no_channel_sharded
+    if channel_sharded:
         def abandon():
             if rank == 0:
                 res["channel_sharded"] = {"error": f"abandoned after {args.leg_timeout:.0f} s (RCCL leg hung)"}
@@ -538,9 +584,9 @@ def main():
         cs = run_guarded(lambda: channel_sharded_leg(args.steps, args.warmup, world, rank, local, dist),
                          args.leg_timeout, rank, abandon)
     if rank == 0:
-        if not args.no_channel_sharded:
+        if channel_sharded:
             res["channel_sharded"] = cs
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(taps, args.cpu_seconds)
         print(json.dumps(res), flush=True)
     if dist is not None:

@@ -439,8 +439,8 @@ def bench_c4(args):
 
 # ------------------------------------------------------------------------------ c5
 def bench_c5(args):
-    """configs[4] through bench.channel_sharded_leg (the same leg bench.py adds to the
-    driver's line): resident bank rate, RCCL scatterv / gatherv each timed on its own, end to
+    """configs[4] through bench.channel_sharded_leg (the same leg bench.py --full adds to
+    the driver's line): resident bank rate, RCCL scatterv / gatherv each timed on its own, end to
     end, and a float64 spot check of one channel per rank after the gather on the root."""
     import scipy.signal as ss
     import bench

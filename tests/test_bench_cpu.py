@@ -60,6 +60,34 @@ def test_committed_pmc_file_matches_the_shipped_kernel():
     assert 1.0 <= t / (10 * (1 << 28)) <= 1.1
 
 
+def test_dump_blocks_fixed_sample():
+    """--dump-outputs: a short output is written whole; of a long one the first block, the last
+    (possibly short) block and seeded others, ascending, disjoint, in bounds, at most 64 MB as
+    f32 pairs, and the same on every call."""
+    B, NB = bench.DUMP_BLOCK, bench.DUMP_NBLOCKS
+    assert bench.dump_blocks(0) == []
+    assert bench.dump_blocks(5) == [(0, 5)]
+    assert bench.dump_blocks(B * NB) == [(0, B * NB)]
+    for n_out in (B * NB + 1, 1 << 26, (1 << 26) + 77):
+        bl = bench.dump_blocks(n_out)
+        assert bl == bench.dump_blocks(n_out) and len(bl) == NB
+        assert bl[0] == (0, B) and bl[-1][0] + bl[-1][1] == n_out and 0 < bl[-1][1] <= B
+        assert all(s % B == 0 and c == B for s, c in bl[:-1])
+        assert all(a[0] + a[1] <= b[0] for a, b in zip(bl, bl[1:]))
+        assert 8 * sum(c for _, c in bl) <= 64 << 20
+
+
+def test_plain_run_leaves_the_extra_legs_to_full(monkeypatch):
+    """A plain run times the headline only: the channel-sharded leg and the CPU baseline take
+    runs of their own and need --full (where --no-* still drops one)."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and not a.no_cpu_baseline and not a.no_channel_sharded
+
+
 def test_channel_sharded_leg_guard_exception_and_hang():
     """bench.run_guarded: a failing leg becomes an "error" entry; a hung leg (a peer that died
     inside an RCCL collective) fires the watchdog, which emits the line and exits NON-zero
