@@ -14,7 +14,7 @@ import pytest
 
 
 def tap_scale_exp(taps):
-    # fir_mfma.hip fir_mx_prepare: 15 - e, max|h| = m 2^e, m in [0.5, 1)
+    # fir_select.cpp FirPaths::mx_prepare: 15 - e, max|h| = m 2^e, m in [0.5, 1)
     hmax = float(np.max(np.abs(taps)))
     return min(126, max(-126, 15 - np.frexp(np.float32(hmax))[1]))
 

@@ -90,32 +90,40 @@ struct AsyncD2H {
                 return SDRGPU_ERR_DEVICE;
         return SDRGPU_OK;
     }
-    // next slot with `bytes[a]` of device staging per output array; `s` (the compute stream)
-    // waits for the slot's previous download before anything later on it writes the slot
-    int acquire(hipStream_t s, const size_t* bytes, int narrays, int* slot) {
+    // A block's preamble.  The input staging buffer holds in_bytes: if it must grow, the compute
+    // stream `s` is drained first (growing frees a buffer an earlier block may still read).  Then
+    // the next slot, with bytes[a] of device staging per output array; growing one waits for the
+    // downloads in flight, and `s` waits for the slot's previous download before anything
+    // enqueued on it afterwards (the block's kernels) writes the slot.
+    int begin(hipStream_t s, DevBuf& stage_in, size_t in_bytes, const size_t* bytes, int narrays,
+              int* slot) {
         int st = init();
         if (st) return st;
+        if (stage_in.cap < in_bytes) {
+            SDRGPU_HIP_TRY(hipStreamSynchronize(s));
+            if ((st = stage_in.ensure(in_bytes))) return st;
+        }
         const int k = next;
         next = (next + 1) % kSlots;
         for (int a = 0; a < narrays; ++a)
             if (out[k][a].cap < bytes[a]) {
-                if (hipStreamSynchronize(d2h) != hipSuccess) return SDRGPU_ERR_DEVICE;
+                SDRGPU_HIP_TRY(hipStreamSynchronize(d2h));
                 live[k] = false;
                 if ((st = out[k][a].ensure(bytes[a]))) return st;
             }
-        if (live[k] && hipStreamWaitEvent(s, ev_o[k], 0) != hipSuccess) return SDRGPU_ERR_DEVICE;
+        if (live[k]) SDRGPU_HIP_TRY(hipStreamWaitEvent(s, ev_o[k], 0));
         *slot = k;
         return SDRGPU_OK;
     }
-    // after the producing kernel on `s`: the download stream waits for it
-    int begin_download(hipStream_t s, int slot) {
-        if (hipEventRecord(ev_k[slot], s) != hipSuccess ||
-            hipStreamWaitEvent(d2h, ev_k[slot], 0) != hipSuccess)
-            return SDRGPU_ERR_DEVICE;
-        return SDRGPU_OK;
-    }
-    int end_download(int slot) {
-        if (hipEventRecord(ev_o[slot], d2h) != hipSuccess) return SDRGPU_ERR_DEVICE;
+    // A block's tail, after its kernels on `s`: the download stream waits for them, then copies
+    // bytes[a] of the slot's array a to host[a].
+    int download(hipStream_t s, int slot, void* const* host, const size_t* bytes, int narrays) {
+        SDRGPU_HIP_TRY(hipEventRecord(ev_k[slot], s));
+        SDRGPU_HIP_TRY(hipStreamWaitEvent(d2h, ev_k[slot], 0));
+        for (int a = 0; a < narrays; ++a)
+            SDRGPU_HIP_TRY(hipMemcpyAsync(host[a], out[slot][a].ptr, bytes[a],
+                                          hipMemcpyDeviceToHost, d2h));
+        SDRGPU_HIP_TRY(hipEventRecord(ev_o[slot], d2h));
         live[slot] = true;
         return SDRGPU_OK;
     }

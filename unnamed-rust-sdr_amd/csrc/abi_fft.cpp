@@ -317,23 +317,13 @@ int sdrgpu_stft_process_async(sdrgpu_stft* h, const void* in, size_t n_in, void*
     sdrgpu_fft& f = h->fft;
     const size_t ib = n_in * kind_bytes(h->in_kind), ob = nf * (size_t)f.n * f.out_elem();
     int st, slot = 0;
-    if (f.stage_in.cap < ib) {  // growing frees a buffer an earlier block may still read
-        SDRGPU_HIP_TRY(hipStreamSynchronize(f.stream.cur));
-        if ((st = f.stage_in.ensure(ib))) return st;
-    }
-    const size_t obytes[1] = {ob ? ob : 8};
-    if ((st = f.async.acquire(f.stream.cur, obytes, 1, &slot))) return st;
+    const size_t cap = ob ? ob : 8;
+    if ((st = f.async.begin(f.stream.cur, f.stage_in, ib, &cap, 1, &slot))) return st;
     SDRGPU_HIP_TRY(hipMemcpyAsync(f.stage_in.ptr, in, ib, hipMemcpyHostToDevice, f.stream.cur));
     size_t got = 0;
     if ((st = sdrgpu_stft_process_dev(h, f.stage_in.ptr, n_in, f.async.out[slot][0].ptr, nf, &got)))
         return st;
-    if (ob) {
-        if ((st = f.async.begin_download(f.stream.cur, slot))) return st;
-        SDRGPU_HIP_TRY(hipMemcpyAsync(out, f.async.out[slot][0].ptr, ob, hipMemcpyDeviceToHost,
-                                      f.async.d2h));
-        if ((st = f.async.end_download(slot))) return st;
-    }
-    return SDRGPU_OK;
+    return ob ? f.async.download(f.stream.cur, slot, &out, &ob, 1) : SDRGPU_OK;
 }
 
 int sdrgpu_stft_set_input_kind(sdrgpu_stft* h, int sample_kind) {

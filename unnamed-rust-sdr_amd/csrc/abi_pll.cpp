@@ -386,12 +386,8 @@ int sdrgpu_pll_process_async(sdrgpu_pll* h, const void* in, size_t n, float* out
     const size_t nch = (size_t)h->dp.nch;
     const size_t sb = h->dp.in_u8 ? 2 : sizeof(float2);
     int st, slot = 0;
-    if (h->stage_in.cap < nch * n * sb) {  // growing frees a buffer an earlier block may read
-        SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
-        if ((st = h->stage_in.ensure(nch * n * sb))) return st;
-    }
     const size_t ob[2] = {nch * n * sizeof(float), nch * n};
-    if ((st = h->async.acquire(h->stream.cur, ob, 2, &slot))) return st;
+    if ((st = h->async.begin(h->stream.cur, h->stage_in, nch * n * sb, ob, 2, &slot))) return st;
     SDRGPU_HIP_TRY(hipMemcpyAsync(h->stage_in.ptr, in, nch * n * sb, hipMemcpyHostToDevice,
                                   h->stream.cur));
     float* d_out = static_cast<float*>(h->async.out[slot][0].ptr);
@@ -401,10 +397,8 @@ int sdrgpu_pll_process_async(sdrgpu_pll* h, const void* in, size_t n, float* out
     if ((st = pll_launch(h->dp, h->stage_in.ptr, (long)n, (long)n, d_out, d_lock, (long)n,
                          h->d_state, sp, h->stream.cur)) || (st = h->probe(sp)))
         return st;
-    if ((st = h->async.begin_download(h->stream.cur, slot))) return st;
-    SDRGPU_HIP_TRY(hipMemcpyAsync(out, d_out, ob[0], hipMemcpyDeviceToHost, h->async.d2h));
-    SDRGPU_HIP_TRY(hipMemcpyAsync(locked, d_lock, ob[1], hipMemcpyDeviceToHost, h->async.d2h));
-    return h->async.end_download(slot);
+    void* const host[2] = {out, locked};
+    return h->async.download(h->stream.cur, slot, host, ob, 2);
 }
 
 int sdrgpu_pll_state(sdrgpu_pll* h, size_t ch, float* nphase, float* value_re_im) {

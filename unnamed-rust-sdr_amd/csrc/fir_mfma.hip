@@ -33,11 +33,9 @@
 // 16 segments per wave, one 256-lane workgroup per CU.  Algorithmic bytes per input sample
 // at D=4: 8 in + 2 out = 10 B; MFMA work 6 x (K+15D rounded to 32) / (16 x 16) per output.
 #include <algorithm>
-#include <cmath>
-#include <cstdlib>
 
 #include "fir_exact.hpp"
-#include "fir_mxi.hpp"
+#include "fir_select.hpp"
 
 namespace sdrgpu {
 
@@ -298,15 +296,6 @@ void fir_mx_kernel(MxParams p) {
     }
 }
 
-struct MxState {
-    int K = 0, D = 0, NCH = 0;
-    float* d_taps = nullptr;
-    void* d_dummy = nullptr;  // zeroed target of fir_mxh's clamped prefetches
-    int tap_scale_exp = 0;    // fir_mxh: 15 - exponent(max |h|)
-    bool taps_finite = true;  // fir_mxi takes integer taps: finite ones only
-    int cus = 256;
-};
-
 int mx_nch(int K, int D) {
     if (!(D == 2 || D == 4 || D == 8)) return 0;
     // smallest instantiated chunk count covering the K + 15D + 1 window
@@ -321,88 +310,22 @@ int mx_nch(int K, int D) {
 
 }  // namespace
 
-int fir_mx_supported(int sample_kind, int tap_kind, int K, int D) {
-    if (fir_mxh_shape_ok(sample_kind, tap_kind, K, D)) return 1;
-    if (sample_kind != SDRGPU_C64 || tap_kind != SDRGPU_F32) return 0;
-    if (!(D == 2 || D == 4 || D == 8) || K < 1) return 0;
-    return mx_nch(K, D) > 0;
-}
+// Host entry points (declared in fir_select.hpp; the taps and the CU count come from the
+// selector's shared MFMA state).
+int fir_mx3_shape_ok(int K, int D) { return K >= 1 && mx_nch(K, D) > 0; }
 
-void* fir_mx_prepare(int device, const float* taps, int K, int D, int* status) {
-    if (!fir_mx_supported(SDRGPU_C64, SDRGPU_F32, K, D)) {
-        if (status) *status = SDRGPU_ERR_UNSUPPORTED;
-        return nullptr;
-    }
-    auto* st = new MxState();
-    st->K = K;
-    st->D = D;
-    st->NCH = mx_nch(K, D);
-    {
-        float hmax = 0.f;
-        for (int k = 0; k < K; ++k) {
-            hmax = std::max(hmax, std::fabs(taps[k]));
-            if (!std::isfinite(taps[k])) st->taps_finite = false;
-        }
-        int e = 0;
-        (void)std::frexp(hmax, &e);
-        st->tap_scale_exp = std::min(126, std::max(-126, 15 - e));
-    }
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess &&
-        cus > 0)
-        st->cus = cus;
-    if (hipMalloc(&st->d_taps, sizeof(float) * K) != hipSuccess ||
-        hipMemcpy(st->d_taps, taps, sizeof(float) * K, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(&st->d_dummy, fir_mxh_dummy_bytes()) != hipSuccess ||
-        hipMemset(st->d_dummy, 0, fir_mxh_dummy_bytes()) != hipSuccess) {
-        if (st->d_taps) (void)hipFree(st->d_taps);
-        if (st->d_dummy) (void)hipFree(st->d_dummy);
-        delete st;
-        if (status) *status = SDRGPU_ERR_NOMEM;
-        return nullptr;
-    }
-    if (status) *status = SDRGPU_OK;
-    return st;
-}
-
-void fir_mx_release(void* state) {
-    auto* st = static_cast<MxState*>(state);
-    if (!st) return;
-    if (st->d_taps) (void)hipFree(st->d_taps);
-    if (st->d_dummy) (void)hipFree(st->d_dummy);
-    delete st;
-}
-
-int fir_mx_launch(const FirParams& fp, void* state, hipStream_t s, int* kernel) {
-    int dummy_kernel = 0;
-    int& kern = kernel ? *kernel : dummy_kernel;
-    auto* st = static_cast<MxState*>(state);
-    if (st && fp.sample_kind == SDRGPU_CU8) {  // rtl_tcp u8 ingest fused into the FIR load
-        if (fp.D != st->D || fp.K != st->K) return SDRGPU_ERR_UNSUPPORTED;
-        // the int8-MFMA kernel (16-byte aligned channels), else the fp16 one (4-byte aligned)
-        if (st->taps_finite && fir_mxi_supported(fp, st->tap_scale_exp)) {
-            kern = SDRGPU_FIR_KERNEL_INT8;
-            return fir_mxi_launch(fp, st->d_taps, st->tap_scale_exp, st->d_dummy, st->cus, s);
-        }
-        if (!fir_mxh_supported(fp)) return SDRGPU_ERR_UNSUPPORTED;
-        kern = SDRGPU_FIR_KERNEL_FP16;
-        return fir_mxh_launch(fp, st->d_taps, st->tap_scale_exp, st->d_dummy, st->cus, s);
-    }
-    if (!st || fp.sample_kind != SDRGPU_C64 || fp.tap_kind != SDRGPU_F32 || fp.D != st->D ||
-        fp.K != st->K)
-        return SDRGPU_ERR_UNSUPPORTED;
-    // D = 4, 2 and 1: the LDS-staged fp16 two-way split at two waves per SIMD (fir_mxh.hip);
-    // D = 8 (and D = 2 blocks the fp16 kernel does not take): the register-fed exact bf16
-    // three-way split below
-    if (fir_mxh_supported(fp)) {
-        kern = SDRGPU_FIR_KERNEL_FP16;
-        return fir_mxh_launch(fp, st->d_taps, st->tap_scale_exp, st->d_dummy, st->cus, s);
-    }
-    if (st->NCH == 0) return SDRGPU_ERR_UNSUPPORTED;  // shape only the fp16 kernel covers
+int fir_mx3_supported(const FirParams& fp) {
+    if (fp.sample_kind != SDRGPU_C64 || fp.tap_kind != SDRGPU_F32) return 0;
+    if (!fir_mx3_shape_ok(fp.K, fp.D)) return 0;
     // 16-byte loads of sample pairs: channel bases must stay 16-byte aligned
     if ((reinterpret_cast<uintptr_t>(fp.in) & 15) != 0 || (fp.nch > 1 && (fp.ld_in & 1)))
-        return SDRGPU_ERR_UNSUPPORTED;
-    const int D = st->D, NCH = st->NCH, NACC = NCH / (D / 2);
+        return 0;
+    return 1;
+}
+
+int fir_mx3_launch(const FirParams& fp, const float* d_taps, int cus, hipStream_t s) {
+    if (!fir_mx3_supported(fp)) return SDRGPU_ERR_UNSUPPORTED;
+    const int D = fp.D, NCH = mx_nch(fp.K, D), NACC = NCH / (D / 2);
     MxParams p;
     p.in = static_cast<const float2*>(fp.in);
     p.ld_in = fp.ld_in;
@@ -412,7 +335,7 @@ int fir_mx_launch(const FirParams& fp, void* state, hipStream_t s, int* kernel) 
     p.i0 = fp.i0;
     p.n_out = fp.n_out;
     p.K = fp.K;
-    p.taps = st->d_taps;
+    p.taps = d_taps;
     // window end E = i0 + (m + 16t + 15) D + 1 has the parity of i0 + 1 (D even, m % 16 = 0)
     p.delta = (int)((fp.i0 + 1) & 1);
     p.out = static_cast<float2*>(fp.out);
@@ -421,7 +344,7 @@ int fir_mx_launch(const FirParams& fp, void* state, hipStream_t s, int* kernel) 
     p.tpp = fp.tpp;
     p.taps_pm = fp.taps_pm;
     // segments: one wave per SIMD chip-wide, 16 segments per wave
-    const long target = 16L * 4 * st->cus;
+    const long target = 16L * 4 * cus;
     const long total = fp.n_out * (long)fp.nch;
     long seg = ceil_div(std::max(1L, total), target);
     seg = std::max(64L, ceil_div(seg, 16) * 16);
@@ -434,7 +357,6 @@ int fir_mx_launch(const FirParams& fp, void* state, hipStream_t s, int* kernel) 
     dim3 grid((unsigned)std::max(1L, ceil_div(waves, kMxBlock / 64)));
 #define SDRGPU_MX_CASE(DD, CC)                                                                   \
     if (D == DD && NCH == CC) {                                                                  \
-        kern = SDRGPU_FIR_KERNEL_BF16X3;                                                         \
         hipLaunchKernelGGL((fir_mx_kernel<DD, CC>), grid, dim3(kMxBlock), 0, s, p);                \
         SDRGPU_LAUNCH_CHECK();                                                                   \
         return SDRGPU_OK;                                                                        \

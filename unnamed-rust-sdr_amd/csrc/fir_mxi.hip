@@ -407,10 +407,14 @@ int mxi_nc(int K, int D) {
 
 }  // namespace
 
+int fir_mxi_shape_ok(int K, int D) {
+    if (!(D == 8 || D == 4 || D == 2 || D == 1) || K < 1 || K > 257) return 0;
+    return mxi_nc(K, D) > 0;
+}
+
 int fir_mxi_supported(const FirParams& fp, int tap_scale_exp) {
     if (fp.sample_kind != SDRGPU_CU8 || fp.tap_kind != SDRGPU_F32) return 0;
-    if (!(fp.D == 8 || fp.D == 4 || fp.D == 2 || fp.D == 1) || fp.K < 1 || fp.K > 257) return 0;
-    if (mxi_nc(fp.K, fp.D) == 0 || fp.i0 < 0 || fp.i0 >= fp.D) return 0;
+    if (!fir_mxi_shape_ok(fp.K, fp.D) || fp.i0 < 0 || fp.i0 >= fp.D) return 0;
     // taps as 23-bit integers: 2^S and the output scale 2^-(S + 7) stay normal floats
     if (tap_scale_exp + 14 > 126 || tap_scale_exp + 7 < -126) return 0;
     // 16-byte loads of 8 samples: channel bases stay 16-byte aligned

@@ -1,0 +1,136 @@
+// fir_select.cpp -- which FIR kernel runs a block.  FirPaths::launch is the whole decision: the
+// kernels in order of preference, each behind its own eligibility test (fir_*_supported).
+#include "fir_select.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+namespace sdrgpu {
+
+using detail::DeviceGuard;
+
+// Shapes some MFMA kernel covers: what SDRGPU_FIR_MATRIX accepts, and when the shared MFMA state
+// is worth building.  Each kernel answers for itself.  The fused u8 kernels' shapes (fir_mxi:
+// D in {1, 2, 4, 8} with K <= 257; fir_mxh u8: D = 4 with K <= 257, mxh_nch) lie inside the c64
+// kernels' that a converted block reaches (fir_mxh: K <= 257 / 257 / 273 at D = 4 / 2 / 1;
+// bf16x3: K <= 257 / 259 / 263 at D = 2 / 4 / 8, mx_nch), so for a u8 stream the answer equals
+// the c64 one and the u8 terms change no answer: they state that the fused kernels are asked.
+bool FirPaths::mx_shape_ok() const {
+    if (tk != SDRGPU_F32 || sk == SDRGPU_F32) return false;
+    if (sk == SDRGPU_CU8 && (fir_mxi_shape_ok(K, D) || fir_mxh_shape_ok(SDRGPU_CU8, tk, K, D)))
+        return true;
+    return fir_mxh_shape_ok(SDRGPU_C64, tk, K, D) || fir_mx3_shape_ok(K, D);
+}
+
+bool FirPaths::os_shape_ok() const {
+    return fir_os_supported(sk == SDRGPU_CU8 ? SDRGPU_C64 : sk, tk, K, D) != 0;
+}
+
+int FirPaths::prepare(int dev, int sample_kind, int tap_kind, const void* h, int ntaps, int decim) {
+    device = dev;
+    sk = sample_kind;
+    tk = tap_kind;
+    K = ntaps;
+    D = decim;
+    const auto* b = static_cast<const unsigned char*>(h);
+    taps.assign(b, b + detail::kind_bytes(tk) * (size_t)K);
+    return SDRGPU_OK;  // the device state is built by the first block that needs it
+}
+
+void FirPaths::release() {
+    DeviceGuard g(device);
+    if (mx.d_taps) (void)hipFree(mx.d_taps);
+    if (mx.d_dummy) (void)hipFree(mx.d_dummy);
+    mx = Mx();
+    mx_tried = false;
+    if (os_state) fir_os_release(os_state);
+    os_state = nullptr;
+    stage_conv.release();
+}
+
+int FirPaths::set_algorithm(int a) {
+    if (a < SDRGPU_FIR_AUTO || a > SDRGPU_FIR_MATRIX) return SDRGPU_ERR_INVALID;
+    if (a == SDRGPU_FIR_OVERLAP_SAVE && !os_shape_ok()) return SDRGPU_ERR_UNSUPPORTED;
+    if (a == SDRGPU_FIR_MATRIX && !mx_shape_ok()) return SDRGPU_ERR_UNSUPPORTED;
+    algo = a;
+    return SDRGPU_OK;
+}
+
+// Natural-order device taps, the zeroed dummy tile and the tap scale; tried once per handle.
+int FirPaths::mx_prepare() {
+    if (mx_tried) return mx_status;
+    mx_tried = true;
+    const float* h = reinterpret_cast<const float*>(taps.data());
+    float hmax = 0.f;
+    for (int k = 0; k < K; ++k) {
+        hmax = std::max(hmax, std::fabs(h[k]));
+        if (!std::isfinite(h[k])) mx.taps_finite = false;
+    }
+    int e = 0;
+    (void)std::frexp(hmax, &e);
+    mx.tap_scale_exp = std::min(126, std::max(-126, 15 - e));
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess &&
+        cus > 0)
+        mx.cus = cus;
+    const bool ok = hipMalloc(&mx.d_taps, sizeof(float) * K) == hipSuccess &&
+                    hipMemcpy(mx.d_taps, h, sizeof(float) * K, hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMalloc(&mx.d_dummy, fir_mxh_dummy_bytes()) == hipSuccess &&
+                    hipMemset(mx.d_dummy, 0, fir_mxh_dummy_bytes()) == hipSuccess;
+    return mx_status = ok ? SDRGPU_OK : SDRGPU_ERR_NOMEM;
+}
+
+int FirPaths::launch(FirParams& p, hipStream_t s, int* ran_algo, int* kernel) {
+    const bool try_mx = (algo == SDRGPU_FIR_AUTO || algo == SDRGPU_FIR_MATRIX) && mx_shape_ok();
+    const bool try_os = (algo == SDRGPU_FIR_AUTO || algo == SDRGPU_FIR_OVERLAP_SAVE) && os_shape_ok();
+    int st, conv = 0;
+    auto ran = [&](int a, int k, int status) {
+        if (status == SDRGPU_OK) *ran_algo = a, *kernel = k | conv;
+        return status;
+    };
+    if (try_mx && (st = mx_prepare())) return st;
+
+    if (try_mx && p.sample_kind == SDRGPU_CU8) {
+        // 1. fused u8 on int8 (16-byte aligned channels), 2. fused u8 on fp16 (4-byte aligned)
+        if (mx.taps_finite && fir_mxi_supported(p, mx.tap_scale_exp))
+            return ran(SDRGPU_FIR_MATRIX, SDRGPU_FIR_KERNEL_INT8,
+                       fir_mxi_launch(p, mx.d_taps, mx.tap_scale_exp, mx.d_dummy, mx.cus, s));
+        if (fir_mxh_supported(p))
+            return ran(SDRGPU_FIR_MATRIX, SDRGPU_FIR_KERNEL_FP16,
+                       fir_mxh_launch(p, mx.d_taps, mx.tap_scale_exp, mx.d_dummy, mx.cus, s));
+    }
+    if (p.sample_kind == SDRGPU_CU8) {
+        // 3. no fused kernel for this block: convert it to c64 (RtlTcpSignal::next), dense rows,
+        // and filter it as c64 from here on
+        if ((st = stage_conv.ensure((size_t)p.nch * p.n_in * sizeof(float2)))) return st;
+        if ((st = cu8_to_c64_launch(p.in, p.ld_in, p.n_in, p.nch, stage_conv.ptr, s))) return st;
+        p.sample_kind = SDRGPU_C64;
+        p.in = stage_conv.ptr;
+        p.ld_in = p.n_in;
+        conv = SDRGPU_FIR_KERNEL_CU8_CONVERTED;
+    }
+    if (try_mx) {
+        // 4. c64 on fp16 (D = 4, 2, 1), 5. c64 on bf16x3 (D = 8, and what fp16 leaves at D = 2, 4);
+        // a block neither takes (unaligned channels) goes on down the list
+        if (fir_mxh_supported(p))
+            return ran(SDRGPU_FIR_MATRIX, SDRGPU_FIR_KERNEL_FP16,
+                       fir_mxh_launch(p, mx.d_taps, mx.tap_scale_exp, mx.d_dummy, mx.cus, s));
+        if (fir_mx3_supported(p))
+            return ran(SDRGPU_FIR_MATRIX, SDRGPU_FIR_KERNEL_BF16X3,
+                       fir_mx3_launch(p, mx.d_taps, mx.cus, s));
+    }
+    if (try_os) {
+        // 6. overlap-save; when it was forced its failure is the answer, else direct still runs
+        if (!os_state && os_status == SDRGPU_OK)
+            os_state = fir_os_prepare(device, p.sample_kind, tk, taps.data(), K, D, s, &os_status);
+        st = os_state ? fir_os_launch(p, os_state, s) : SDRGPU_ERR_UNSUPPORTED;
+        if (st == SDRGPU_OK || algo == SDRGPU_FIR_OVERLAP_SAVE)
+            return ran(SDRGPU_FIR_OVERLAP_SAVE, SDRGPU_FIR_KERNEL_OVERLAP_SAVE, st);
+    }
+    // 7. direct form, every shape: fir_direct_launch (fir_direct.hip) takes the wave-private
+    // direct2 kernel where fir_direct2_supported, else the R-blocked kernel (R = 8, then 2) while
+    // its tile fits the LDS budget, else the naive kernel
+    return ran(SDRGPU_FIR_DIRECT, SDRGPU_FIR_KERNEL_DIRECT, fir_direct_launch(p, s));
+}
+
+}  // namespace sdrgpu
