@@ -126,6 +126,36 @@ def test_biquad_time_parallel_forced(sdr, oracle, seg, warm):
                                       err_msg=f"ch {ch}")
 
 
+def test_biquad_time_parallel_right_guess_overwritten(sdr, oracle):
+    """A right guess overwritten by a wrong re-run.  Lr(75e-6) at 144 kHz is an integrator (pole
+    exactly 1.0): y = b0 on [10, 1500) after x[10] = +1, x[1500] = -1.  With 1024-sample segments
+    and 64 of warm-up, segment 1's guess (0) and pass-1 end (-b0) are wrong, segment 2's guess
+    (0) is the true state but differs from that end, so it is re-run from the wrong state and
+    the walk has to repair it: one miss per pulsed channel, none on the all-zero channel."""
+    nch, n = 3, 3 * 1024 + 40
+    d = sdr.filter.BiquadD.Lr(75e-6)
+    bq = d.design(144000.0, sample_kind=0, nch=nch)
+    assert bq.coefs()[3] == 1.0
+    bq.set_time_parallel(1024, 64)
+    x = np.zeros((nch, n), np.float32)
+    x[[0, 2], 10] = 1.0
+    x[[0, 2], 1500] = -1.0
+    y1 = bq.process(x)
+    assert bq.last_time_parallel() == (4, 2)
+    b0 = bq.coefs()[0]
+    want = np.zeros(n, np.float32)
+    want[10:1500] = b0
+    np.testing.assert_array_equal(y1[0], want)
+    np.testing.assert_array_equal(y1[1], np.zeros(n, np.float32))
+    x2 = np.random.default_rng(79).standard_normal((nch, 2100)).astype(np.float32)
+    y = np.concatenate([y1, bq.process(x2)], axis=1)
+    xx = np.concatenate([x, x2], axis=1)
+    c = d.to_c()
+    for ch in range(nch):
+        np.testing.assert_array_equal(y[ch], oracle.biquad_run(c.kind, c.freq, c.q, 144000.0, xx[ch]),
+                                      err_msg=f"ch {ch}")
+
+
 def test_biquad_time_parallel_not_for_identity_integrator_or_many_channels(sdr):
     """Identity has no recurrence, Lr(75e-6) at 144 kHz rounds its pole to exactly 1.0 in f32
     (an integrator: two trajectories never meet), the pilot's LowPass(20 Hz) at 144 kHz has its

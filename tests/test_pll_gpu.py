@@ -306,7 +306,7 @@ def test_pll_special_operands_bit_exact(sdr, oracle):
                                    f"{np.flatnonzero(bad)[0]}")
 
 
-# ---- time-parallel blocks (pll.hip "speculative segments"): bit-identical to the serial PLL ----
+# ---- time-parallel blocks (time_parallel.hpp "speculative segments"): bit-identical to the serial PLL ----
 
 @pytest.mark.parametrize("seg,warm", [(4096, 4096), (2048, 64), (8192, 16384), (1000, 512)],
                          ids=["converging", "mostly-recomputed", "warm-reaches-start", "ragged"])

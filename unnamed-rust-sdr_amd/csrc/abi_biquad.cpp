@@ -19,11 +19,7 @@ struct sdrgpu_biquad {
     BiquadState* d_state = nullptr;
     StreamSlot stream;
     DevBuf stage_in, stage_out;
-    // time-parallel blocks (biquad.hip): tp_seg / tp_warm 0 = automatic, tp_seg < 0 = serial
-    long tp_seg = 0, tp_warm = 0;
-    long simds = 1024;
-    DevBuf spec_buf;
-    long last_nseg = 0, last_nck = 0;
+    TpPlanner tp;  // time-parallel blocks (time_parallel.hpp)
 
     // Warm-up for two trajectories of this recurrence to agree bit for bit: the slower pole of
     // 1 - na1 z^-1 - na2 z^-2 decays by r per sample, so 48 / -log2(r) samples shrink a start
@@ -52,50 +48,17 @@ struct sdrgpu_biquad {
     // enough segments per channel to give every SIMD one wave (64 channel-segments each), none
     // shorter than 4 warm-ups or 4 Ki samples.
     void plan(long n, long* seg, long* warm) const {
-        *seg = 0;
         const long aw = auto_warm();
-        *warm = tp_warm > 0 ? (tp_warm + 7) / 8 * 8 : aw;
-        if (ident || tp_seg < 0 || n <= 0 || (tp_seg == 0 && aw == 0)) return;
-        long sg;
-        if (tp_seg > 0) {
-            sg = (tp_seg + 7) / 8 * 8;
-        } else {
-            const long minseg = std::max(4 * *warm, 4096L);
-            const long by_lanes = 64 * simds / (long)nch, by_len = n / minseg;
-            const long nseg = by_lanes < by_len ? by_lanes : by_len;
-            if (nseg < 2) return;
-            sg = ((n + nseg - 1) / nseg + 7) / 8 * 8;
-        }
-        if (n > sg) *seg = sg;
+        *warm = tp.warm(aw);
+        *seg = ident || (tp.want_seg == 0 && aw == 0) ? 0 : tp.seg(n, (long)nch, std::max(4 * *warm, 4096L));
     }
+    static constexpr long kMinCk = 512;  // samples between checkpoints, at least
     int make_spec(long n, BqSpec* sp, bool serial = false) {
         plan(n, &sp->seg, &sp->warm);
-        last_nseg = 0;
+        tp.last_nseg = 0;
         if (serial) sp->seg = 0;
         if (sp->seg <= 0) return SDRGPU_OK;
-        sp->nseg = (n + sp->seg - 1) / sp->seg;
-        long ck = sp->seg;  // checkpoints: at most 16 per segment, ck a multiple of 8 dividing seg
-        for (long d = 16; d >= 2; --d)
-            if (sp->seg % (8 * d) == 0 && sp->seg / d >= 512) { ck = sp->seg / d; break; }
-        sp->ck = ck;
-        const size_t nck = (size_t)(sp->seg / ck - 1);
-        const size_t nstate = (size_t)sp->nseg * nch;
-        // guess, end, end2, checkpoints, the counter (at state index (3 + nck) nstate), the marks
-        const size_t bytes = (3 + nck) * nstate * sizeof(BiquadState) + 64 + nstate * sizeof(int);
-        if (bytes > spec_buf.cap) {  // growing frees a buffer an earlier block may still use
-            SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-            int st = spec_buf.ensure(bytes);
-            if (st) return st;
-        }
-        sp->guess = static_cast<BiquadState*>(spec_buf.ptr);
-        sp->end = sp->guess + nstate;
-        sp->end2 = sp->end + nstate;
-        sp->ckpt = nck ? sp->end2 + nstate : nullptr;
-        sp->recomputed = reinterpret_cast<unsigned long long*>(sp->end2 + nstate + nck * nstate);
-        sp->rstop = reinterpret_cast<int*>(sp->recomputed + 8);
-        last_nseg = sp->nseg;
-        last_nck = (long)nck;
-        return SDRGPU_OK;
+        return tp.fill(*sp, n, (long)nch, kMinCk, stream.cur);
     }
 
     size_t sbytes() const { return kind_bytes(sk); }
@@ -105,7 +68,7 @@ struct sdrgpu_biquad {
         d_state = nullptr;
         stage_in.release();
         stage_out.release();
-        spec_buf.release();
+        tp.buf.release();
         stream.destroy();
     }
     int reset() {
@@ -129,9 +92,7 @@ struct sdrgpu_biquad {
         if (!g.ok()) return SDRGPU_ERR_DEVICE;
         if ((st = stream.create())) return st;
         SDRGPU_HIP_TRY(hipMalloc(&d_state, nch * sizeof(BiquadState)));
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
-            simds = 4L * cus;
+        tp.init(device);
         return reset();
     }
     int run_dev(const void* in, size_t ld_in, size_t n, void* out, size_t ld_out) {
@@ -219,8 +180,8 @@ int sdrgpu_biquad_process_dev(sdrgpu_biquad* h, const void* d_in, size_t ld_in, 
 
 int sdrgpu_biquad_set_time_parallel(sdrgpu_biquad* h, long seg, long warm) {
     if (!h || warm < 0) return SDRGPU_ERR_INVALID;
-    h->tp_seg = seg;
-    h->tp_warm = warm;
+    h->tp.want_seg = seg;
+    h->tp.want_warm = warm;
     return SDRGPU_OK;
 }
 
@@ -232,18 +193,8 @@ int sdrgpu_biquad_time_parallel_plan(const sdrgpu_biquad* h, size_t n, long* seg
 
 int sdrgpu_biquad_last_time_parallel(sdrgpu_biquad* h, long* segments, long* recomputed) {
     if (!h || !segments || !recomputed) return SDRGPU_ERR_INVALID;
-    *segments = h->last_nseg;
-    *recomputed = 0;
-    if (h->last_nseg > 0) {
-        DeviceGuard g(h->device);
-        unsigned long long r = 0;
-        const auto* base = static_cast<const BiquadState*>(h->spec_buf.ptr);
-        SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
-        SDRGPU_HIP_TRY(hipMemcpy(&r, base + (3 + h->last_nck) * h->last_nseg * (long)h->nch, sizeof(r),
-                                 hipMemcpyDeviceToHost));
-        *recomputed = (long)r;
-    }
-    return SDRGPU_OK;
+    DeviceGuard g(h->device);
+    return h->tp.last(h->stream.cur, segments, recomputed);
 }
 
 int sdrgpu_biquad_sync(sdrgpu_biquad* h) {
@@ -264,8 +215,8 @@ int sdrgpu_biquad_clone(const sdrgpu_biquad* h, sdrgpu_biquad** out) {
     auto* c = new (std::nothrow) sdrgpu_biquad();
     if (!c) return SDRGPU_ERR_NOMEM;
     int st = c->init(h->device, h->sk, h->c, h->ident, h->nch);
-    c->tp_seg = h->tp_seg;
-    c->tp_warm = h->tp_warm;
+    c->tp.want_seg = h->tp.want_seg;
+    c->tp.want_warm = h->tp.want_warm;
     if (!st) {
         DeviceGuard g(h->device);
         if (hipMemcpyAsync(c->d_state, h->d_state, h->nch * sizeof(BiquadState),

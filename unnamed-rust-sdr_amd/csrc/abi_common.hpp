@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "time_parallel.hpp"
 
 namespace sdrgpu {
 namespace detail {
@@ -142,6 +143,65 @@ struct AsyncD2H {
         }
         if (d2h) (void)hipStreamDestroy(d2h);
         d2h = nullptr;
+    }
+};
+
+// A handle's time-parallel blocks (time_parallel.hpp; the PLL and the biquad): what the caller
+// asked for, the part of the plan both share, the scratch, the record of the most recent block.
+struct TpPlanner {
+    long want_seg = 0, want_warm = 0;  // set_time_parallel: 0 = automatic, want_seg < 0 = always serial
+    long simds = 1024;
+    DevBuf buf;
+    long last_nseg = 0;  // segments of the most recent block (0: one serial pass)
+    const unsigned long long* last_counter = nullptr;  // and its count of missed guesses
+
+    void init(int device) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
+            simds = 4L * cus;
+    }
+    long warm(long automatic) const { return want_warm > 0 ? (want_warm + 7) / 8 * 8 : automatic; }
+    // Segment length for a block of n samples, a multiple of 8; 0 = one serial pass.  Automatic:
+    // enough segments per channel to give every SIMD one wave (64 channel-segments each), none
+    // shorter than minseg.
+    long seg(long n, long nch, long minseg) const {
+        if (want_seg < 0 || n <= 0) return 0;
+        long sg = want_seg;
+        if (want_seg == 0) {
+            const long by_lanes = 64 * simds / nch, by_len = n / minseg;
+            const long nseg = by_lanes < by_len ? by_lanes : by_len;
+            if (nseg < 2) return 0;
+            sg = (n + nseg - 1) / nseg;
+        }
+        sg = (sg + 7) / 8 * 8;
+        return n > sg ? sg : 0;
+    }
+    // Completes the plan sp (seg and warm set, seg > 0) for a block of n samples on nch channels:
+    // the segment count, checkpoints no closer than min_ck, the scratch pointers.
+    template <class State>
+    int fill(TpSpec<State>& sp, long n, long nch, long min_ck, hipStream_t s) {
+        sp.nseg = (n + sp.seg - 1) / sp.seg;
+        sp.ck = tp_checkpoint_interval(sp.seg, min_ck);
+        const size_t bytes = tp_scratch_bytes(sp, nch);
+        if (bytes > buf.cap) {  // growing frees a buffer an earlier block may still use
+            SDRGPU_HIP_TRY(hipStreamSynchronize(s));
+            if (int st = buf.ensure(bytes)) return st;
+        }
+        tp_lay_out(sp, nch, buf.ptr);
+        last_nseg = sp.nseg;
+        last_counter = sp.recomputed;
+        return SDRGPU_OK;
+    }
+    // (segments, missed guesses) of the most recent block, once the stream s has finished it
+    int last(hipStream_t s, long* segments, long* recomputed) const {
+        *segments = last_nseg;
+        *recomputed = 0;
+        if (last_nseg <= 0) return SDRGPU_OK;
+        unsigned long long r = 0;
+        SDRGPU_HIP_TRY(hipStreamSynchronize(s));
+        SDRGPU_HIP_TRY(hipMemcpy(&r, last_counter, sizeof(r), hipMemcpyDeviceToHost));
+        *recomputed = (long)r;
+        return SDRGPU_OK;
     }
 };
 

@@ -69,13 +69,7 @@ struct sdrgpu_pll {
     StreamSlot stream;
     DevBuf stage_in, stage_out, stage_lock;
     AsyncD2H async;
-    // time-parallel segments (pll.hip): requested segment / warm-up lengths (0 = auto, segment
-    // < 0 = always one serial pass), the device's SIMD count, and the [2][segments][nch] states
-    long tp_seg = 0, tp_warm = 0;
-    long simds = 1024;
-    DevBuf spec_buf;
-    long last_nseg = 0;  // segments of the most recent time-parallel block (0: serial)
-    long last_nck = 0;   // and the checkpoints per segment it kept
+    TpPlanner tp;  // time-parallel segments (time_parallel.hpp)
     // Automatic plan, adapted per handle: when most segments of a time-parallel block had to be
     // recomputed (an unlocked loop on noise: trajectories that never meet bit for bit), the next
     // kSerialBlocks blocks run one serial pass and the handle then probes again.  The recompute
@@ -92,7 +86,7 @@ struct sdrgpu_pll {
     bool phase_on = false;
 
     bool adapt_serial() {
-        if (tp_seg != 0) return false;
+        if (tp.want_seg != 0) return false;
         if (probe_pending && hipEventQuery(probe_ev) == hipSuccess) {
             probe_pending = false;
             if (2 * (long)*probe_host > probe_total) serial_left = kSerialBlocks;
@@ -105,12 +99,12 @@ struct sdrgpu_pll {
     }
     // after a launch: record this block's recompute count for the next plans
     int probe(const PllSpec& sp) {
-        if (tp_seg != 0 || sp.seg <= 0 || probe_pending || !probe_ev) return SDRGPU_OK;
+        if (tp.want_seg != 0 || sp.seg <= 0 || probe_pending || !probe_ev) return SDRGPU_OK;
         SDRGPU_HIP_TRY(hipMemcpyAsync(probe_host, sp.recomputed, sizeof(*probe_host), hipMemcpyDeviceToHost,
                                       stream.cur));
         SDRGPU_HIP_TRY(hipEventRecord(probe_ev, stream.cur));
         probe_pending = true;
-        probe_total = last_nseg * dp.nch;
+        probe_total = tp.last_nseg * dp.nch;
         return SDRGPU_OK;
     }
 
@@ -122,56 +116,21 @@ struct sdrgpu_pll {
     // 8 Ki to 16 Ki of warm-up all at 11.4-13.2 ms (profiles/r05_pll_refix_sweep.txt); one
     // 1.8 Msps stream in main.rs's 0.1 s blocks, 4 Ki segments 6.2 ms per block against 9.7 at
     // the 16 Ki minimum and 53 serially, 2 Ki segments 20 ms (profiles/r05_pll_tp_single.txt).
-    static constexpr long kMinSeg = 4096, kWarm = 4096;
+    static constexpr long kMinSeg = 4096, kWarm = 4096, kMinCk = 1024;  // kMinCk: between checkpoints
     void plan(long n, long* seg, long* warm) const {
-        *seg = 0;
-        *warm = tp_warm > 0 ? (tp_warm + 7) / 8 * 8 : kWarm;
-        if (tp_seg < 0 || n <= 0) return;
-        long sg;
-        if (tp_seg > 0) {
-            sg = (tp_seg + 7) / 8 * 8;
-        } else {
-            const long by_lanes = 64 * simds / dp.nch, by_len = n / kMinSeg;
-            const long nseg = by_lanes < by_len ? by_lanes : by_len;
-            if (nseg < 2) return;
-            sg = ((n + nseg - 1) / nseg + 7) / 8 * 8;
-        }
-        if (n > sg) *seg = sg;
+        *warm = tp.warm(kWarm);
+        *seg = tp.seg(n, dp.nch, kMinSeg);
     }
 
     int make_spec(long n, PllSpec* sp, bool serial = false) {
         plan(n, &sp->seg, &sp->warm);
-        last_nseg = 0;
+        tp.last_nseg = 0;
         if (sp->seg > 0 && adapt_serial()) serial = true;
         if (serial) sp->seg = 0;
         if (sp->seg <= 0) return SDRGPU_OK;
-        const long nseg = (n + sp->seg - 1) / sp->seg;
-        // checkpoints every ck samples: at most 16 per segment, ck a multiple of 8 dividing seg
-        long ck = sp->seg;
-        for (long d = 16; d >= 2; --d)
-            if (sp->seg % (8 * d) == 0 && sp->seg / d >= 1024) { ck = sp->seg / d; break; }
-        sp->ck = ck;
-        const size_t nck = (size_t)(sp->seg / ck - 1);
-        const size_t nstate = (size_t)nseg * (size_t)dp.nch;
-        // guess, end, end2, checkpoints, the counter (sdrgpu_pll_last_time_parallel reads it at
-        // state index (3 + nck) nstate), then the re-run marks
-        const size_t bytes = (3 + nck) * nstate * sizeof(PllChannelState) + nstate * sizeof(int) + 64;
-        if (bytes > spec_buf.cap) {  // growing frees a buffer an earlier block may still use
-            SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-            int st = spec_buf.ensure(bytes);
-            if (st) return st;
-        }
-        sp->guess = static_cast<PllChannelState*>(spec_buf.ptr);
-        sp->end = sp->guess + nseg * dp.nch;
-        sp->end2 = sp->end + nstate;
-        sp->ckpt = nck ? sp->end2 + nstate : nullptr;
-        sp->recomputed = reinterpret_cast<unsigned long long*>(sp->end2 + nstate + nck * nstate);
-        sp->rstop = reinterpret_cast<int*>(sp->recomputed + 8);
-        sp->phase_ev = phase_on ? phase_ev : nullptr;
-        last_nseg = nseg;
-        last_nck = (long)nck;
-        return SDRGPU_OK;
+        return tp.fill(*sp, n, dp.nch, kMinCk, stream.cur);
     }
+    hipEvent_t* phase() { return phase_on ? phase_ev : nullptr; }
 
     void free_all() {
         DeviceGuard g(device);
@@ -189,7 +148,7 @@ struct sdrgpu_pll {
         stage_in.release();
         stage_out.release();
         stage_lock.release();
-        spec_buf.release();
+        tp.buf.release();
         stream.destroy();
     }
 };
@@ -236,10 +195,7 @@ int sdrgpu_pll_create(int device, const sdrgpu_pll_params* p, size_t nch, sdrgpu
         if (!st && (hipHostMalloc(reinterpret_cast<void**>(&h->probe_host), sizeof(*h->probe_host)) != hipSuccess ||
                     hipEventCreateWithFlags(&h->probe_ev, hipEventDisableTiming) != hipSuccess))
             st = SDRGPU_ERR_NOMEM;
-        int cus = 0;
-        if (!st && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess &&
-            cus > 0)
-            h->simds = 4L * cus;
+        if (!st) h->tp.init(device);
     }
     if (!st) st = sdrgpu_pll_reset(h);
     if (st) {
@@ -266,8 +222,8 @@ int sdrgpu_pll_set_output_mode(sdrgpu_pll* h, int mode) {
 
 int sdrgpu_pll_set_time_parallel(sdrgpu_pll* h, long seg, long warm) {
     if (!h || warm < 0) return SDRGPU_ERR_INVALID;
-    h->tp_seg = seg;
-    h->tp_warm = warm;
+    h->tp.want_seg = seg;
+    h->tp.want_warm = warm;
     return SDRGPU_OK;
 }
 
@@ -279,18 +235,8 @@ int sdrgpu_pll_time_parallel_plan(const sdrgpu_pll* h, size_t n, long* seg, long
 
 int sdrgpu_pll_last_time_parallel(sdrgpu_pll* h, long* segments, long* recomputed) {
     if (!h || !segments || !recomputed) return SDRGPU_ERR_INVALID;
-    *segments = h->last_nseg;
-    *recomputed = 0;
-    if (h->last_nseg > 0) {
-        DeviceGuard g(h->device);
-        unsigned long long r = 0;
-        const auto* base = static_cast<const PllChannelState*>(h->spec_buf.ptr);
-        SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
-        SDRGPU_HIP_TRY(hipMemcpy(&r, base + (3 + h->last_nck) * h->last_nseg * h->dp.nch, sizeof(r),
-                                 hipMemcpyDeviceToHost));
-        *recomputed = (long)r;
-    }
-    return SDRGPU_OK;
+    DeviceGuard g(h->device);
+    return h->tp.last(h->stream.cur, segments, recomputed);
 }
 
 int sdrgpu_pll_set_phase_timing(sdrgpu_pll* h, int on) {
@@ -305,7 +251,7 @@ int sdrgpu_pll_set_phase_timing(sdrgpu_pll* h, int on) {
 int sdrgpu_pll_last_phase_ms(sdrgpu_pll* h, float* pass1, float* rerun, float* walk) {
     if (!h || !pass1 || !rerun || !walk) return SDRGPU_ERR_INVALID;
     *pass1 = *rerun = *walk = 0.f;
-    if (!h->phase_on || h->last_nseg <= 0) return SDRGPU_OK;
+    if (!h->phase_on || h->tp.last_nseg <= 0) return SDRGPU_OK;
     DeviceGuard g(h->device);
     SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
     SDRGPU_HIP_TRY(hipEventElapsedTime(pass1, h->phase_ev[0], h->phase_ev[1]));
@@ -341,7 +287,7 @@ int sdrgpu_pll_process_dev(sdrgpu_pll* h, const void* d_in, size_t ld_in, size_t
     int st = h->make_spec((long)n, &sp, alias);
     if (st) return st;
     if ((st = pll_launch(h->dp, d_in, (long)ld_in, (long)n, d_out, d_locked, (long)ld_out, h->d_state, sp,
-                         h->stream.cur)))
+                         h->phase(), h->stream.cur)))
         return st;
     return h->probe(sp);
 }
@@ -366,7 +312,7 @@ int sdrgpu_pll_process(sdrgpu_pll* h, const void* in, size_t ld_in, size_t n, fl
                                     hipMemcpyHostToDevice, h->stream.cur));
     if ((st = pll_launch(h->dp, h->stage_in.ptr, (long)n, (long)n,
                          static_cast<float*>(h->stage_out.ptr), static_cast<uint8_t*>(h->stage_lock.ptr),
-                         (long)n, h->d_state, sp, h->stream.cur)) || (st = h->probe(sp)))
+                         (long)n, h->d_state, sp, h->phase(), h->stream.cur)) || (st = h->probe(sp)))
         return st;
     SDRGPU_HIP_TRY(hipMemcpy2DAsync(out, ld_out * sizeof(float), h->stage_out.ptr, n * sizeof(float),
                                     n * sizeof(float), nch, hipMemcpyDeviceToHost, h->stream.cur));
@@ -395,7 +341,7 @@ int sdrgpu_pll_process_async(sdrgpu_pll* h, const void* in, size_t n, float* out
     PllSpec sp;
     if ((st = h->make_spec((long)n, &sp))) return st;
     if ((st = pll_launch(h->dp, h->stage_in.ptr, (long)n, (long)n, d_out, d_lock, (long)n,
-                         h->d_state, sp, h->stream.cur)) || (st = h->probe(sp)))
+                         h->d_state, sp, h->phase(), h->stream.cur)) || (st = h->probe(sp)))
         return st;
     void* const host[2] = {out, locked};
     return h->async.download(h->stream.cur, slot, host, ob, 2);
@@ -428,8 +374,8 @@ int sdrgpu_pll_clone(const sdrgpu_pll* h, sdrgpu_pll** out) {
     if (st) return st;
     (*out)->dp.out_mode = h->dp.out_mode;
     (*out)->dp.in_u8 = h->dp.in_u8;
-    (*out)->tp_seg = h->tp_seg;
-    (*out)->tp_warm = h->tp_warm;
+    (*out)->tp.want_seg = h->tp.want_seg;
+    (*out)->tp.want_warm = h->tp.want_warm;
     DeviceGuard g(h->device);
     SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
     SDRGPU_HIP_TRY(hipMemcpy((*out)->d_state, h->d_state, h->dp.nch * sizeof(PllChannelState),

@@ -110,23 +110,45 @@ __device__ __forceinline__ void bq_run(const float (&c)[5], BiquadState& s, cons
     }
 }
 
-// Time-parallel blocks, the PLL's scheme (pll.hip) on a linear recurrence:
-// a stable biquad forgets its output history geometrically, so a copy started `warm` samples
-// early from zero output history (x1 / x2 are the block's own inputs, exact) reaches the true
-// (y1, y2) bit for bit, typically within a few pole time constants.  bq_seg_kernel: one lane
-// per channel-segment, warm-up (state only), the guess at the segment start, the segment's
-// outputs with checkpoints every ck samples, its end state.  bq_refix_kernel: every segment
-// whose guess differs from its predecessor's pass-1 end is re-run from that end state, up to
-// the checkpoint where it meets its own pass-1 trajectory.  bq_fix_kernel: per channel, in
-// order, with the true state: a segment whose guess was true and was not overwritten, or whose
-// re-run started from the true state, is exact; any other is recomputed serially.  Every
-// output is the serial recurrence's.
-__device__ __forceinline__ bool bq_same(const BiquadState& a, const BiquadState& b) {
-    return __float_as_uint(a.y1r) == __float_as_uint(b.y1r) && __float_as_uint(a.y2r) == __float_as_uint(b.y2r) &&
-           __float_as_uint(a.y1i) == __float_as_uint(b.y1i) && __float_as_uint(a.y2i) == __float_as_uint(b.y2i) &&
-           __float_as_uint(a.x1r) == __float_as_uint(b.x1r) && __float_as_uint(a.x2r) == __float_as_uint(b.x2r) &&
-           __float_as_uint(a.x1i) == __float_as_uint(b.x1i) && __float_as_uint(a.x2i) == __float_as_uint(b.x2i);
-}
+// Time-parallel blocks: the speculative segments of time_parallel.hpp on a linear recurrence.  A
+// stable biquad forgets its output history geometrically, so a copy started `warm` samples early
+// from zero output history (x1 / x2 are the block's own inputs, exact) reaches the true (y1, y2)
+// bit for bit, typically within a few pole time constants.  A warm-up start needs the two inputs
+// before it, so one that would begin at sample 0 or 1 runs from the carried state instead.
+template <bool CPLX>
+struct BqTp {
+    using State = BiquadState;
+    static constexpr int kWords = sizeof(BiquadState) / sizeof(float);
+    static constexpr int W = CPLX ? 2 : 1;  // floats per sample
+    const float c[5];
+    const float* __restrict__ x;
+    float* __restrict__ y;
+    BiquadState* __restrict__ carried;
+    unsigned long long* __restrict__ missed;
+    // channel ch of the block; carried_: its carried state (the re-run pass has none)
+    __device__ BqTp(float b0, float b1, float b2, float na1, float na2, const float* in, long ld_in, float* out,
+                    long ld_out, long ch, BiquadState* carried_, unsigned long long* missed_)
+        : c{b0, b1, b2, na1, na2}, x(in + ch * ld_in * W), y(out + ch * ld_out * W), carried(carried_),
+          missed(missed_) {}
+    static __device__ __forceinline__ long warm_from(long t0, long warm) { return t0 - warm < 2 ? 0 : t0 - warm; }
+    __device__ __forceinline__ State load() const { return *carried; }
+    __device__ __forceinline__ void store(const State& s) const { *carried = s; }
+    __device__ __forceinline__ State warm_state(long tw) const {
+        State s{};
+        s.x1r = x[(tw - 1) * W];
+        s.x2r = x[(tw - 2) * W];
+        if (CPLX) {
+            s.x1i = x[(tw - 1) * W + 1];
+            s.x2i = x[(tw - 2) * W + 1];
+        }
+        return s;
+    }
+    template <bool STORE>
+    __device__ __forceinline__ void run(State& s, long a, long b) const {
+        bq_run<CPLX, STORE>(c, s, x, y, a, b);
+    }
+    __device__ __forceinline__ void miss() const { atomicAdd(missed, 1ull); }
+};
 
 template <bool CPLX>
 __global__ __launch_bounds__(kBqBlock) void bq_seg_kernel(long nch, float b0, float b1, float b2,
@@ -138,36 +160,10 @@ __global__ __launch_bounds__(kBqBlock) void bq_seg_kernel(long nch, float b0, fl
     own_simd();
     const long g = (long)blockIdx.x * kBqBlock + threadIdx.x;
     if (g >= nch * sp.nseg) return;
-    constexpr int W = CPLX ? 2 : 1;
     const long ch = g % nch, sg = g / nch;
-    const long t0 = sg * sp.seg, t1 = t0 + sp.seg < n ? t0 + sp.seg : n;
-    long tw = t0 > sp.warm ? t0 - sp.warm : 0;
-    if (tw < 2) tw = 0;  // a warm-up start needs the two inputs before it
-    const float c[5] = {b0, b1, b2, na1, na2};
-    const float* __restrict__ x = in + ch * ld_in * W;
-    float* __restrict__ y = out + ch * ld_out * W;
-    BiquadState s{};
-    if (tw == 0) {
-        s = st[ch];
-    } else {  // zero output history; the input history is the block's own samples
-        s.x1r = x[(tw - 1) * W];
-        s.x2r = x[(tw - 2) * W];
-        if (CPLX) {
-            s.x1i = x[(tw - 1) * W + 1];
-            s.x2i = x[(tw - 2) * W + 1];
-        }
-    }
-    bq_run<CPLX, false>(c, s, x, y, tw, t0);
-    sp.guess[g] = s;
-    const long nck = sp.seg / sp.ck;
-    BiquadState* __restrict__ cp = sp.ckpt + g * (nck - 1);
-    for (long j = 0; j < nck; ++j) {
-        const long a = t0 + j * sp.ck, b = j + 1 < nck ? (a + sp.ck < t1 ? a + sp.ck : t1) : t1;
-        if (a >= b) break;
-        bq_run<CPLX, true>(c, s, x, y, a, b);
-        if (j + 1 < nck) cp[j] = s;
-    }
-    sp.end[g] = s;
+    const BqTp<CPLX> tp(b0, b1, b2, na1, na2, in, ld_in, out, ld_out, ch, const_cast<BiquadState*>(st) + ch,
+                        sp.recomputed);
+    tp_segment(tp, sp, nch, n, ch, sg);
 }
 
 template <bool CPLX>
@@ -179,30 +175,9 @@ __global__ __launch_bounds__(kBqBlock) void bq_refix_kernel(long nch, float b0, 
     own_simd();
     const long g = (long)blockIdx.x * kBqBlock + threadIdx.x;
     if (g < nch || g >= nch * sp.nseg) return;  // segment 0 starts from the carried state
-    constexpr int W = CPLX ? 2 : 1;
     const long ch = g % nch, sg = g / nch;
-    const long t0 = sg * sp.seg, t1 = t0 + sp.seg < n ? t0 + sp.seg : n;
-    if (t0 - sp.warm < 2 || bq_same(sp.guess[g], sp.end[g - nch])) {
-        sp.rstop[g] = 0;
-        return;
-    }
-    const float c[5] = {b0, b1, b2, na1, na2};
-    const float* __restrict__ x = in + ch * ld_in * W;
-    float* __restrict__ y = out + ch * ld_out * W;
-    BiquadState t = sp.end[g - nch];
-    const long nck = sp.seg / sp.ck;
-    const BiquadState* __restrict__ cp = sp.ckpt + g * (nck - 1);
-    int k = 0;
-    bool met = false;
-    for (long j = 0; j < nck && !met; ++j) {
-        const long a = t0 + j * sp.ck, b = j + 1 < nck ? (a + sp.ck < t1 ? a + sp.ck : t1) : t1;
-        if (a >= b) break;
-        bq_run<CPLX, true>(c, t, x, y, a, b);
-        ++k;
-        met = j + 1 < nck && bq_same(cp[j], t);
-    }
-    sp.rstop[g] = met ? k : -k;
-    if (!met) sp.end2[g] = t;
+    const BqTp<CPLX> tp(b0, b1, b2, na1, na2, in, ld_in, out, ld_out, ch, nullptr, sp.recomputed);
+    tp_rerun(tp, sp, nch, n, ch, sg);
 }
 
 template <bool CPLX>
@@ -214,41 +189,8 @@ __global__ __launch_bounds__(kBqBlock) void bq_fix_kernel(long nch, float b0, fl
     own_simd();
     const long ch = (long)blockIdx.x * kBqBlock + threadIdx.x;
     if (ch >= nch) return;
-    constexpr int W = CPLX ? 2 : 1;
-    const float c[5] = {b0, b1, b2, na1, na2};
-    const float* __restrict__ x = in + ch * ld_in * W;
-    float* __restrict__ y = out + ch * ld_out * W;
-    BiquadState t = sp.end[ch];  // segment 0 started from the carried state: exact
-    for (long sg = 1; sg < sp.nseg; ++sg) {
-        const long t0 = sg * sp.seg, t1 = t0 + sp.seg < n ? t0 + sp.seg : n;
-        const long g = sg * nch + ch;
-        const bool hit = t0 - sp.warm < 2 || bq_same(sp.guess[g], t);
-        const int rs = sp.rstop[g];
-        if (hit && rs == 0) {
-            t = sp.end[g];
-            continue;
-        }
-        if (!hit) {
-            atomicAdd(sp.recomputed, 1ull);
-            if (rs != 0 && bq_same(sp.end[g - nch], t)) {  // re-run from the true state: exact
-                t = rs > 0 ? sp.end[g] : sp.end2[g];
-                continue;
-            }
-        }
-        // recompute from the true state up to the first checkpoint it meets, and at least over
-        // the intervals a re-run from a wrong state overwrote
-        const long nck = sp.seg / sp.ck, over = rs < 0 ? -rs : rs;
-        const BiquadState* __restrict__ cp = sp.ckpt + g * (nck - 1);
-        bool met = false;
-        for (long j = 0; j < nck && !(met && j >= over); ++j) {
-            const long a = t0 + j * sp.ck, b = j + 1 < nck ? (a + sp.ck < t1 ? a + sp.ck : t1) : t1;
-            if (a >= b) break;
-            bq_run<CPLX, true>(c, t, x, y, a, b);
-            met = j + 1 < nck && bq_same(cp[j], t);
-        }
-        if (met) t = sp.end[g];
-    }
-    st[ch] = t;
+    const BqTp<CPLX> tp(b0, b1, b2, na1, na2, in, ld_in, out, ld_out, ch, st + ch, sp.recomputed);
+    tp_walk(tp, sp, nch, n, ch);
 }
 
 }  // namespace
@@ -256,10 +198,7 @@ __global__ __launch_bounds__(kBqBlock) void bq_fix_kernel(long nch, float b0, fl
 int biquad_tp_launch(bool cplx, long nch, const float* c, const void* in, long ld_in, long n,
                      void* out, long ld_out, BiquadState* state, const BqSpec& sp, hipStream_t s) {
     if (nch <= 0 || n <= 0) return SDRGPU_OK;
-    if (sp.seg <= 0 || sp.seg % kBqChunk || sp.ck <= 0 || sp.ck % kBqChunk || sp.seg % sp.ck ||
-        sp.nseg != ceil_div(n, sp.seg) || sp.nseg < 2 || !sp.guess || !sp.end || !sp.end2 ||
-        !sp.rstop || !sp.recomputed || (sp.seg / sp.ck > 1 && !sp.ckpt))
-        return SDRGPU_ERR_INVALID;
+    if (!tp_spec_valid(sp, n, kBqChunk)) return SDRGPU_ERR_INVALID;
     SDRGPU_HIP_TRY(hipMemsetAsync(sp.recomputed, 0, sizeof(unsigned long long), s));
     const dim3 gs((unsigned)ceil_div(nch * sp.nseg, kBqBlock)), gc((unsigned)ceil_div(nch, kBqBlock)), b(kBqBlock);
     const float* x = static_cast<const float*>(in);

@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "time_parallel.hpp"
+
 namespace sdrgpu {
 
 // DF1 state of one channel (biquad.rs:4-22): inputs x1, x2 and outputs y1, y2; re / im for
@@ -11,13 +13,7 @@ struct BiquadState {
     float x1r, x1i, x2r, x2i, y1r, y1i, y2r, y2i;
 };
 
-// time-parallel plan and scratch of one block (abi_biquad.cpp; the bq_*_kernel of biquad.hip)
-struct BqSpec {
-    long seg = 0, warm = 0, ck = 0, nseg = 0;
-    BiquadState *guess = nullptr, *end = nullptr, *end2 = nullptr, *ckpt = nullptr;
-    int* rstop = nullptr;
-    unsigned long long* recomputed = nullptr;  // segments whose guess missed (zeroed per block)
-};
+using BqSpec = TpSpec<BiquadState>;  // time_parallel.hpp
 
 // one serial pass per channel (one lane each)
 int biquad_launch(bool cplx, long nch, const float* c, int ident, const void* in, long ld_in,

@@ -247,150 +247,72 @@ __global__ __launch_bounds__(kPllBlock) void pll_kernel(PllDevParams p, const vo
     state[ch] = s;
 }
 
-// Time-parallel PLL ("speculative segments").  The recurrence is serial, but a PLL that is
-// tracking forgets its initial state: from any start, the whole state (NCO phase and value,
-// loop / lock / output filter states) comes to agree BIT FOR BIT with the true trajectory after
-// a few thousand samples of the same input (configs[3]'s FM channels: median 3.4 k, max 12 k
-// samples in 128 channels).  So each channel's block is cut into segments that
-// run at once, one lane each (pll_seg_kernel): a segment first runs `warm` samples of warm-up
-// from the design state (no outputs), records the state it reached at its start (guess), then
-// produces its outputs and records its end state.  pll_fix_kernel (one lane per channel) then
-// walks the segments in order with the TRUE state (segment 0 starts from the carried state;
-// so does every segment whose warm-up reaches back to sample 0): where a segment's guess equals
-// the true state bit for bit, its outputs are exactly the serial ones (same state, same inputs,
-// same arithmetic) and its end state is true; where it differs, the segment is recomputed from
-// the true state.  Every output is therefore the serial PLL's; only the time depends on how
-// many segments have to be recomputed (none, typically; all of them for a chaotic, unlocked
-// loop, which then costs one serial pass more than pll_kernel).
+// Time-parallel blocks: the speculative segments of time_parallel.hpp with the PLL as the
+// recurrence.  A warm-up starts from PllDesign::design's state (pll.rs:57-58), or from the
+// carried state where it reaches back to sample 0; two trajectories have met when every state
+// word before `pad` agrees.
+template <bool U8, bool VEC, class Lane>
+struct PllTp {
+    using State = PllChannelState;
+    static constexpr int kWords = offsetof(PllChannelState, pad) / sizeof(float);
+    const Lane ln;
+    const void* __restrict__ row;
+    float* __restrict__ y;
+    uint8_t* __restrict__ lk;
+    PllChannelState* __restrict__ carried;
+    unsigned long long* __restrict__ missed;
+    // channel ch of the block; carried_: its carried state (the re-run pass has none)
+    __device__ PllTp(const PllDevParams& p, const void* in, long ld_in, float* out, uint8_t* locked, long ld_out,
+                     long ch, PllChannelState* carried_, unsigned long long* missed_)
+        : ln(p), row(static_cast<const char*>(in) + ch * ld_in * (U8 ? 2 : 8)), y(out + ch * ld_out),
+          lk(locked + ch * ld_out), carried(carried_), missed(missed_) {}
+    static __device__ __forceinline__ long warm_from(long t0, long warm) { return t0 > warm ? t0 - warm : 0; }
+    __device__ __forceinline__ State load() const { return *carried; }
+    __device__ __forceinline__ void store(const State& s) const { *carried = s; }
+    __device__ __forceinline__ State warm_state(long) const { return State{}; }
+    template <bool STORE>
+    __device__ __forceinline__ void run(State& s, long a, long b) const {
+        pll_run<U8, VEC, STORE>(ln, s, row, a, b, y, lk);
+    }
+    __device__ __forceinline__ void miss() const { atomicAdd(missed, 1ull); }
+};
+
 template <bool U8, int LID, int OID, int KID, int MODE, bool VEC>
 __global__ __launch_bounds__(kPllBlock) void pll_seg_kernel(
     PllDevParams p, const void* __restrict__ in_, long ld_in, long n, float* __restrict__ out,
-    uint8_t* __restrict__ locked, long ld_out, const PllChannelState* __restrict__ state, long seg,
-    long warm, long nseg, PllChannelState* __restrict__ guess, PllChannelState* __restrict__ endst,
-    long ck, PllChannelState* __restrict__ ckpt) {
+    uint8_t* __restrict__ locked, long ld_out, const PllChannelState* __restrict__ state, PllSpec sp) {
     own_simd();
     const long g = (long)blockIdx.x * kPllBlock + threadIdx.x;
-    if (g >= p.nch * nseg) return;
+    if (g >= p.nch * sp.nseg) return;
     const long ch = g % p.nch, sg = g / p.nch;
-    const long t0 = sg * seg, t1 = t0 + seg < n ? t0 + seg : n, tw = t0 > warm ? t0 - warm : 0;
-    PllChannelState s{};  // PllDesign::design's state (pll.rs:57-58) unless the warm-up starts at 0
-    if (tw == 0) s = state[ch];
-    const PllLane<LID, OID, KID, MODE> ln(p);
-    const void* row = static_cast<const char*>(in_) + ch * ld_in * (U8 ? 2 : 8);
-    pll_run<U8, VEC, false>(ln, s, row, tw, t0, nullptr, nullptr);
-    guess[g] = s;
-    // the segment in checkpoint intervals: a recomputation from the true state can stop where
-    // it meets this trajectory (pll_fix_kernel)
-    const long nck = seg / ck;
-    PllChannelState* __restrict__ cp = ckpt + g * (nck - 1);
-    for (long j = 0; j < nck; ++j) {
-        const long a = t0 + j * ck, b = j + 1 < nck ? (a + ck < t1 ? a + ck : t1) : t1;
-        if (a >= b) break;
-        pll_run<U8, VEC, true>(ln, s, row, a, b, out + ch * ld_out, locked + ch * ld_out);
-        if (j + 1 < nck) cp[j] = s;
-    }
-    endst[g] = s;
+    const PllTp<U8, VEC, PllLane<LID, OID, KID, MODE>> tp(p, in_, ld_in, out, locked, ld_out, ch,
+                                                          const_cast<PllChannelState*>(state) + ch, sp.recomputed);
+    tp_segment(tp, sp, p.nch, n, ch, sg);
 }
 
-__device__ __forceinline__ bool same_state(const PllChannelState& a, const PllChannelState& b) {
-    const unsigned* x = reinterpret_cast<const unsigned*>(&a);
-    const unsigned* y = reinterpret_cast<const unsigned*>(&b);
-    bool eq = true;
-#pragma unroll
-    for (int i = 0; i < (int)(offsetof(PllChannelState, pad) / sizeof(float)); ++i) eq &= x[i] == y[i];
-    return eq;
-}
-
-// Parallel re-run of the segments whose warm-up missed.  A segment's true start state is the
-// previous segment's end state, and pass 1's end state of the previous segment IS that state
-// whenever the previous segment ended on the true trajectory (its guess was right, or its
-// trajectory met the true one before its end -- the common case).  So every segment whose guess
-// differs from pass 1's end of its predecessor is re-run at once, one lane each, from that end
-// state, until it meets its own pass-1 trajectory at a checkpoint (rstop = +intervals run) or
-// to its end (rstop = -intervals, end state in end2).  pll_fix_kernel then only checks, per
-// channel and in order, that each re-run started from the true state; where one did not
-// (its predecessor's pass-1 end was not true), it recomputes that segment serially as before.
 template <bool U8, int LID, int OID, int KID, int MODE, bool VEC>
 __global__ __launch_bounds__(kPllBlock) void pll_refix_kernel(
     PllDevParams p, const void* __restrict__ in_, long ld_in, long n, float* __restrict__ out,
-    uint8_t* __restrict__ locked, long ld_out, long seg, long warm, long nseg,
-    const PllChannelState* __restrict__ guess, const PllChannelState* __restrict__ endst, long ck,
-    const PllChannelState* __restrict__ ckpt, int* __restrict__ rstop,
-    PllChannelState* __restrict__ end2) {
+    uint8_t* __restrict__ locked, long ld_out, PllSpec sp) {
     own_simd();
     const long g = (long)blockIdx.x * kPllBlock + threadIdx.x;
-    if (g < p.nch || g >= p.nch * nseg) return;  // segment 0 starts from the carried state
+    if (g < p.nch || g >= p.nch * sp.nseg) return;  // segment 0 starts from the carried state
     const long ch = g % p.nch, sg = g / p.nch;
-    const long t0 = sg * seg, t1 = t0 + seg < n ? t0 + seg : n;
-    if (t0 <= warm || same_state(guess[g], endst[g - p.nch])) {
-        rstop[g] = 0;
-        return;
-    }
-    const PllLane<LID, OID, KID, MODE> ln(p);
-    const void* row = static_cast<const char*>(in_) + ch * ld_in * (U8 ? 2 : 8);
-    PllChannelState t = endst[g - p.nch];
-    const long nck = seg / ck;
-    const PllChannelState* __restrict__ cp = ckpt + g * (nck - 1);
-    int k = 0;
-    bool met = false;
-    for (long j = 0; j < nck && !met; ++j) {
-        const long a = t0 + j * ck, b = j + 1 < nck ? (a + ck < t1 ? a + ck : t1) : t1;
-        if (a >= b) break;
-        pll_run<U8, VEC, true>(ln, t, row, a, b, out + ch * ld_out, locked + ch * ld_out);
-        ++k;
-        met = j + 1 < nck && same_state(cp[j], t);
-    }
-    rstop[g] = met ? k : -k;
-    if (!met) end2[g] = t;
+    const PllTp<U8, VEC, PllLane<LID, OID, KID, MODE>> tp(p, in_, ld_in, out, locked, ld_out, ch, nullptr,
+                                                          sp.recomputed);
+    tp_rerun(tp, sp, p.nch, n, ch, sg);
 }
 
 template <bool U8, int LID, int OID, int KID, int MODE, bool VEC>
 __global__ __launch_bounds__(kPllBlock) void pll_fix_kernel(
     PllDevParams p, const void* __restrict__ in_, long ld_in, long n, float* __restrict__ out,
-    uint8_t* __restrict__ locked, long ld_out, PllChannelState* __restrict__ state, long seg,
-    long warm, long nseg, const PllChannelState* __restrict__ guess,
-    const PllChannelState* __restrict__ endst, unsigned long long* __restrict__ recomputed, long ck,
-    const PllChannelState* __restrict__ ckpt, const int* __restrict__ rstop,
-    const PllChannelState* __restrict__ end2) {
+    uint8_t* __restrict__ locked, long ld_out, PllChannelState* __restrict__ state, PllSpec sp) {
     own_simd();
     const long ch = (long)blockIdx.x * kPllBlock + threadIdx.x;
     if (ch >= p.nch) return;
-    const PllLane<LID, OID, KID, MODE> ln(p);
-    const void* row = static_cast<const char*>(in_) + ch * ld_in * (U8 ? 2 : 8);
-    PllChannelState t = endst[ch];  // segment 0 started from the carried state: exact
-    for (long sg = 1; sg < nseg; ++sg) {
-        const long t0 = sg * seg, t1 = t0 + seg < n ? t0 + seg : n;
-        const long g = sg * p.nch + ch;
-        const bool hit = t0 <= warm || same_state(guess[g], t);
-        const int rs = rstop[g];
-        if (hit && rs == 0) {  // pass 1 ran from the true state and nothing overwrote it
-            t = endst[g];
-            continue;
-        }
-        if (!hit) {
-            atomicAdd(recomputed, 1ull);
-            if (rs != 0 && same_state(endst[g - p.nch], t)) {  // re-run from the true state: exact
-                t = rs > 0 ? endst[g] : end2[g];
-                continue;
-            }
-        }
-        // the warm-up did not reach the true state and no re-run started from it, or a re-run
-        // from a wrong state (its predecessor's pass-1 end) overwrote outputs of a segment whose
-        // guess was right: this segment again from the true state, up to the first checkpoint
-        // its trajectory meets (from there on it is exact) and at least over the overwritten
-        // intervals
-        const long nck = seg / ck, over = rs < 0 ? -rs : rs;
-        const PllChannelState* __restrict__ cp = ckpt + g * (nck - 1);
-        bool met = false;
-        for (long j = 0; j < nck && !(met && j >= over); ++j) {
-            const long a = t0 + j * ck, b = j + 1 < nck ? (a + ck < t1 ? a + ck : t1) : t1;
-            if (a >= b) break;
-            pll_run<U8, VEC, true>(ln, t, row, a, b, out + ch * ld_out, locked + ch * ld_out);
-            met = j + 1 < nck && same_state(cp[j], t);
-        }
-        if (met) t = endst[g];
-    }
-    state[ch] = t;
+    const PllTp<U8, VEC, PllLane<LID, OID, KID, MODE>> tp(p, in_, ld_in, out, locked, ld_out, ch, state + ch,
+                                                          sp.recomputed);
+    tp_walk(tp, sp, p.nch, n, ch);
 }
 
 // Output modes 0 and 1 with vector rows (configs[3]'s 1024 channels, main.rs's single
@@ -563,31 +485,25 @@ __global__ __launch_bounds__(2 * kPllBlock) void pll_split_kernel(
 template <bool U8, int LID, int OID, int KID, int MODE>
 void launch_cfg(const PllDevParams& p, const void* in, long ld_in, long n, float* out,
                 uint8_t* locked, long ld_out, PllChannelState* state, const PllSpec& spec,
-                hipStream_t s) {
+                hipEvent_t* ev, hipStream_t s) {
     const long nblk = (p.nch + kPllBlock - 1) / kPllBlock;
     const size_t sb = U8 ? 2 : 8;
     const bool vec = (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (ld_in * sb) % 16 == 0 &&
                      (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (ld_out % 8) == 0 &&
                      (reinterpret_cast<uintptr_t>(locked) & 7) == 0;
-    if (spec.seg > 0 && n > spec.seg) {  // time-parallel segments (seg, warm multiples of kChunk)
-        const long nseg = (n + spec.seg - 1) / spec.seg;
-        const long sblk = (p.nch * nseg + kPllBlock - 1) / kPllBlock;
+    if (spec.seg > 0) {  // time-parallel segments (pll_launch has checked the spec)
+        const long sblk = (p.nch * spec.nseg + kPllBlock - 1) / kPllBlock;
 #define SDRGPU_PLL_SEG(V)                                                                          \
-        if (spec.phase_ev) (void)hipEventRecord(spec.phase_ev[0], s);                              \
+        if (ev) (void)hipEventRecord(ev[0], s);                                                    \
         hipLaunchKernelGGL((pll_seg_kernel<U8, LID, OID, KID, MODE, V>), dim3((unsigned)sblk),      \
-                           dim3(kPllBlock), 0, s, p, in, ld_in, n, out, locked, ld_out, state,       \
-                           spec.seg, spec.warm, nseg, spec.guess, spec.end, spec.ck, spec.ckpt);    \
-        if (spec.phase_ev) (void)hipEventRecord(spec.phase_ev[1], s);                              \
+                           dim3(kPllBlock), 0, s, p, in, ld_in, n, out, locked, ld_out, state, spec); \
+        if (ev) (void)hipEventRecord(ev[1], s);                                                    \
         hipLaunchKernelGGL((pll_refix_kernel<U8, LID, OID, KID, MODE, V>), dim3((unsigned)sblk),    \
-                           dim3(kPllBlock), 0, s, p, in, ld_in, n, out, locked, ld_out, spec.seg,   \
-                           spec.warm, nseg, spec.guess, spec.end, spec.ck, spec.ckpt, spec.rstop,   \
-                           spec.end2);                                                              \
-        if (spec.phase_ev) (void)hipEventRecord(spec.phase_ev[2], s);                              \
+                           dim3(kPllBlock), 0, s, p, in, ld_in, n, out, locked, ld_out, spec);       \
+        if (ev) (void)hipEventRecord(ev[2], s);                                                    \
         hipLaunchKernelGGL((pll_fix_kernel<U8, LID, OID, KID, MODE, V>), dim3((unsigned)nblk),      \
-                           dim3(kPllBlock), 0, s, p, in, ld_in, n, out, locked, ld_out, state,       \
-                           spec.seg, spec.warm, nseg, spec.guess, spec.end, spec.recomputed,        \
-                           spec.ck, spec.ckpt, spec.rstop, spec.end2);                              \
-        if (spec.phase_ev) (void)hipEventRecord(spec.phase_ev[3], s)
+                           dim3(kPllBlock), 0, s, p, in, ld_in, n, out, locked, ld_out, state, spec); \
+        if (ev) (void)hipEventRecord(ev[3], s)
         if (vec) { SDRGPU_PLL_SEG(true); } else { SDRGPU_PLL_SEG(false); }
 #undef SDRGPU_PLL_SEG
         return;
@@ -606,16 +522,16 @@ void launch_cfg(const PllDevParams& p, const void* in, long ld_in, long n, float
 template <bool U8>
 void launch_any(const PllDevParams& p, const void* in, long ld_in, long n, float* out,
                 uint8_t* locked, long ld_out, PllChannelState* state, const PllSpec& spec,
-                hipStream_t s) {
+                hipEvent_t* ev, hipStream_t s) {
     const int l = p.loop_ident, o = p.out_ident, k = p.lock_ident, m = p.out_mode;
     if (!l && o && !k && m == 0)            // src/main.rs:41-46
-        launch_cfg<U8, 0, 1, 0, 0>(p, in, ld_in, n, out, locked, ld_out, state, spec, s);
+        launch_cfg<U8, 0, 1, 0, 0>(p, in, ld_in, n, out, locked, ld_out, state, spec, ev, s);
     else if (!l && !o && !k && m == 0)      // examples/pll.rs:9-15
-        launch_cfg<U8, 0, 0, 0, 0>(p, in, ld_in, n, out, locked, ld_out, state, spec, s);
+        launch_cfg<U8, 0, 0, 0, 0>(p, in, ld_in, n, out, locked, ld_out, state, spec, ev, s);
     else if (!l && !o && !k && m == 1)      // the stereo pilot, src/main.rs:55-66
-        launch_cfg<U8, 0, 0, 0, 1>(p, in, ld_in, n, out, locked, ld_out, state, spec, s);
+        launch_cfg<U8, 0, 0, 0, 1>(p, in, ld_in, n, out, locked, ld_out, state, spec, ev, s);
     else
-        launch_cfg<U8, 2, 2, 2, 2>(p, in, ld_in, n, out, locked, ld_out, state, spec, s);
+        launch_cfg<U8, 2, 2, 2, 2>(p, in, ld_in, n, out, locked, ld_out, state, spec, ev, s);
 }
 
 }  // namespace
@@ -652,16 +568,14 @@ int libm_debug_launch(int fn, const float* a, const float* b, float* o0, float* 
 
 int pll_launch(const PllDevParams& p, const void* in, long ld_in, long n, float* out,
                uint8_t* locked, long ld_out, PllChannelState* state, const PllSpec& spec,
-               hipStream_t s) {
+               hipEvent_t* ev, hipStream_t s) {
     if (n <= 0) return SDRGPU_OK;
-    if (spec.seg > 0 && (spec.seg % kChunk || spec.warm % kChunk || !spec.guess || !spec.end ||
-                         !spec.recomputed || spec.ck <= 0 || spec.ck % kChunk || spec.seg % spec.ck ||
-                         (spec.seg / spec.ck > 1 && !spec.ckpt) || !spec.rstop || !spec.end2))
-        return SDRGPU_ERR_INVALID;
-    if (spec.seg > 0 && n > spec.seg)
+    if (spec.seg > 0) {
+        if (spec.warm % kChunk || !tp_spec_valid(spec, n, kChunk)) return SDRGPU_ERR_INVALID;
         SDRGPU_HIP_TRY(hipMemsetAsync(spec.recomputed, 0, sizeof(unsigned long long), s));
-    if (p.in_u8) launch_any<true>(p, in, ld_in, n, out, locked, ld_out, state, spec, s);
-    else launch_any<false>(p, in, ld_in, n, out, locked, ld_out, state, spec, s);
+    }
+    if (p.in_u8) launch_any<true>(p, in, ld_in, n, out, locked, ld_out, state, spec, ev, s);
+    else launch_any<false>(p, in, ld_in, n, out, locked, ld_out, state, spec, ev, s);
     SDRGPU_LAUNCH_CHECK();
     return SDRGPU_OK;
 }

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "time_parallel.hpp"
 
 namespace sdrgpu {
 
@@ -25,29 +26,14 @@ struct PllChannelState {
     float pad;
 };
 
-// Time-parallel plan of one block (pll.hip, "speculative segments"): seg > 0 cuts each
-// channel's n samples into ceil(n / seg) segments run concurrently, each after `warm` samples
-// of warm-up from the design state; guess / end hold [segments][nch] states (the state each
-// segment's warm-up reached at its start, and the state at its end).  seg == 0: one serial pass.
-struct PllSpec {
-    long seg = 0, warm = 0;
-    PllChannelState* guess = nullptr;
-    PllChannelState* end = nullptr;
-    unsigned long long* recomputed = nullptr;  // segments pll_fix_kernel ran again (zeroed per block)
-    long ck = 0;                               // checkpoint interval inside a segment
-    PllChannelState* ckpt = nullptr;           // [segments][nch][seg / ck - 1] states at t0 + j ck
-    // parallel re-run (pll_refix_kernel): per segment, +k = re-run from the previous segment's
-    // end met this trajectory after k intervals, -k = ran k intervals without meeting it (end
-    // state in end2), 0 = not re-run
-    int* rstop = nullptr;
-    PllChannelState* end2 = nullptr;
-    // optional: four events recorded around pass 1, the re-run pass and the walk
-    hipEvent_t* phase_ev = nullptr;
-};
+// seg == 0: one serial pass over the block; otherwise the time-parallel plan of time_parallel.hpp
+// (seg and warm multiples of 8).  phase_ev, optional: four events recorded around pass 1, the
+// re-run pass and the walk.
+using PllSpec = TpSpec<PllChannelState>;
 
 int pll_launch(const PllDevParams& p, const void* in, long ld_in, long n, float* out,
                uint8_t* locked, long ld_out, PllChannelState* state, const PllSpec& spec,
-               hipStream_t s);
+               hipEvent_t* phase_ev, hipStream_t s);
 
 // test-only: the device atan2f (fn 0) / sincosf (fn 1) restatements over n operands
 int libm_debug_launch(int fn, const float* a, const float* b, float* o0, float* o1, long n,
