@@ -47,11 +47,18 @@ int fir_os_supported(int sample_kind, int tap_kind, int K, int D);
 // LDS-staged direct form on a per-tile scaled two-way fp16 split, two waves per SIMD
 // (fir_mxh.hip): D = 4 (K <= 257, also u8 input), D = 2 (K <= 257) and D = 1 (K <= 273).  tap_scale_exp:
 // taps are multiplied by 2^tap_scale_exp before the split.  d_dummy: fir_mxh_dummy_bytes()
-// of zeroed device memory (target of the clamped prefetches at a stream's end).
+// of zeroed device memory (target of the clamped prefetches at a stream's end).  d_frags: the
+// handle's tap fragment table, fir_mxh_frag_bytes(K, D) bytes (0: no kernel here covers (K, D))
+// filled once by fir_mxh_frag_build from the same d_taps / tap_scale_exp -- the MFMA A operands
+// of every decimation phase, which the kernel's waves load instead of rebuilding them; whoever
+// replaces d_taps rebuilds the table.
 size_t fir_mxh_dummy_bytes();
+size_t fir_mxh_frag_bytes(int K, int D);
+int fir_mxh_frag_build(const float* d_taps, int K, int D, int tap_scale_exp, void* d_frags,
+                       hipStream_t s);
 int fir_mxh_supported(const FirParams& p);
 int fir_mxh_shape_ok(int sample_kind, int tap_kind, int K, int D);  // c64: D in {1, 2, 4}; u8: D = 4
 int fir_mxh_launch(const FirParams& p, const float* d_taps, int tap_scale_exp,
-                   const void* d_dummy, int cus, hipStream_t s);
+                   const void* d_frags, const void* d_dummy, int cus, hipStream_t s);
 
 }  // namespace sdrgpu

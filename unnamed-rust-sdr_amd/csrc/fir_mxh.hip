@@ -56,6 +56,7 @@ constexpr int kBlock = 64 * kWaves;
 constexpr int kCs1 = 4;
 // D = 2 tiles: two 256-output column sets over one 1024-sample window (the D = 4 raw pipeline)
 constexpr int kCs2 = 2;
+constexpr int cs_of(int D) { return D == 1 ? kCs1 : (D == 2 ? kCs2 : 1); }
 // D = 4 runs.  c64 samples: runs of 2 tiles dealt grid-strided, so at any moment the whole
 // chip streams one contiguous window (2048 waves x 16 KiB): 0.441 ms, against 0.460 for the
 // same runs in per-workgroup ranges, 0.486-0.488 for per-workgroup runs of 8 (round 3 s3), and
@@ -109,7 +110,8 @@ struct MxhParams {
     int K;
     int delta;  // 3 - i0
     int sh;     // tap scale exponent
-    const float* taps;
+    const float* taps;   // natural order (exact_tile)
+    const u32x4* frags;  // this delta's tap fragments, [hi / lo][NCH][64 lanes] (tap_frag_kernel)
     float2* out;
     long ld_out;
     long tpc, spc, seg_tiles, units;  // host-checked < 2^31 (tile cursors are 32-bit)
@@ -324,6 +326,44 @@ __device__ __forceinline__ void exact_tile(const MxhParams& p, long ch, int tile
 
 __device__ __forceinline__ float exp2i(int s) { return __builtin_amdgcn_ldexpf(1.0f, s); }
 
+// Scaled tap Toeplitz fragments (fp16 hi / lo), the A operands of a tile's MFMAs.  They depend on
+// (taps, K, sh, delta, D, NCH) only, so a handle builds them once per decimation phase into a
+// table (one block of 64 lanes per delta; fir_mxh_frag_build) and every wave of every launch
+// loads its 2 NCH fragments from it: [delta][hi / lo][NCH][lane], 16 B each.
+template <int NCH, int D>
+__global__ __launch_bounds__(64) void tap_frag_kernel(const float* __restrict__ taps, int K, int sh,
+                                                      u32x4* __restrict__ tab) {
+    constexpr int HR = GeoH<NCH, D, cs_of(D)>::HR;
+    const int lane = threadIdx.x, delta = blockIdx.x;
+    const int g = lane >> 4, v = lane & 15;
+    const float tsc = exp2i(sh);
+    u32x4* __restrict__ th = tab + (size_t)delta * (2 * NCH * 64);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        u32x4 ah, al;
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            unsigned hw = 0, lw = 0;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int pidx = 32 * c + 8 * g + 2 * jj + e;
+                const int k = D * v + D - 1 - delta + HR - pidx;
+                const bool ok = (k >= 0) & (k < K);
+                const float hk = taps[ok ? k : 0];
+                const float hs = ok ? hk * tsc : 0.f;
+                const _Float16 h16 = (_Float16)hs;
+                const _Float16 l16 = (_Float16)(hs - (float)h16);
+                hw |= (unsigned)__builtin_bit_cast(unsigned short, h16) << (16 * e);
+                lw |= (unsigned)__builtin_bit_cast(unsigned short, l16) << (16 * e);
+            }
+            ah[jj] = hw;
+            al[jj] = lw;
+        }
+        th[c * 64 + lane] = ah;
+        th[(NCH + c) * 64 + lane] = al;
+    }
+}
+
 // Samples are streamed once: non-temporal loads and output stores.
 // U8: interleaved u8 I/Q input (rtl_tcp ingest fused into the load, 2 B per sample); the
 // samples are exact integers after a fixed x128 scale, so no per-tile scale, no lo planes,
@@ -335,7 +375,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void fir_mxh_kernel(MxhParams p) {
     using Raw = std::conditional_t<U8, unsigned, float4>;
     using G = GeoH<NCH, D, CS>;
-    constexpr int H = G::H, HR = G::HR, PLB = G::PLB, NH = G::NH, NG = G::NG;
+    constexpr int H = G::H, PLB = G::PLB, NH = G::NH, NG = G::NG;
     constexpr int TI = G::TI;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -353,54 +393,39 @@ void fir_mxh_kernel(MxhParams p) {
     const int K = p.K;
     const int base = wv * G::WAVE;
 
-    // ---- A: scaled tap Toeplitz fragments (fp16 hi / lo) ----
+    // A: the scaled tap Toeplitz fragments (fp16 hi / lo) and the LDS read / write bases are set
+    // up by ramp_setup below, after the wave's first sample loads have been issued
     u32x4 ah[NCH], al[NCH];
-    {
-        const float tsc = exp2i(p.sh);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                unsigned hw = 0, lw = 0;
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int pidx = 32 * c + 8 * g + 2 * jj + e;
-                    const int k = D * v + D - 1 - p.delta + HR - pidx;
-                    const bool ok = (k >= 0) & (k < K);
-                    const float hk = p.taps[ok ? k : 0];
-                    const float hs = ok ? hk * tsc : 0.f;
-                    const _Float16 h16 = (_Float16)hs;
-                    const _Float16 l16 = (_Float16)(hs - (float)h16);
-                    hw |= (unsigned)__builtin_bit_cast(unsigned short, h16) << (16 * e);
-                    lw |= (unsigned)__builtin_bit_cast(unsigned short, l16) << (16 * e);
-                }
-                ah[c][jj] = hw;
-                al[c][jj] = lw;
-            }
-        }
-    }
-
     const int sv = D == 4 ? sigma(v) : v;
     int rb[NCH];
+    int wb0;
+    auto ramp_setup = [&]() {
+        // plain loads: the table (2 NCH KiB per delta) stays L2-resident across waves and launches
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        if constexpr (D == 4) {
-            const int r = sv + (c >> 1);
-            rb[c] = base + 128 * r + 16 * ((4 * (c & 1) + g) ^ ((r >> 1) & 7));
-        } else if constexpr (D == 2) {
-            // 64-byte rows (32 samples), row r = v + c, 16-byte unit g ^ ((r >> 1) & 3): every
-            // 16-lane group of a fragment read hits distinct banks (fir_mxi.hip's D = 4 layout)
-            const int r = v + c;
-            rb[c] = base + 64 * r + 16 * (g ^ ((r >> 1) & 3));
-        } else {
-            rb[c] = base + 2 * (G::OFF + 16 * sv + 32 * c + 8 * g);
+        for (int c = 0; c < NCH; ++c) {
+            ah[c] = p.frags[c * 64 + lane];
+            al[c] = p.frags[(NCH + c) * 64 + lane];
         }
-    }
-    // D = 2: sample s of a 128-sample group at 64 (s >> 5) + 16 (((s >> 3) & 3) ^ ((s >> 6) & 3))
-    // + 2 (s & 7); group k adds 256 k and flips unit bit 1 when k is odd
-    const int wb0 = D == 4   ? base + 128 * (lane >> 5) + 4 * (lane & 3) + 16 * ((lane >> 2) & 7)
-                    : D == 2 ? base + 64 * (lane >> 4) + 4 * (lane & 3) + 16 * (((lane >> 2) & 3) ^ (lane >> 5))
-                             : base + 4 * lane;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            if constexpr (D == 4) {
+                const int r = sv + (c >> 1);
+                rb[c] = base + 128 * r + 16 * ((4 * (c & 1) + g) ^ ((r >> 1) & 7));
+            } else if constexpr (D == 2) {
+                // 64-byte rows (32 samples), row r = v + c, 16-byte unit g ^ ((r >> 1) & 3): every
+                // 16-lane group of a fragment read hits distinct banks (fir_mxi.hip's D = 4 layout)
+                const int r = v + c;
+                rb[c] = base + 64 * r + 16 * (g ^ ((r >> 1) & 3));
+            } else {
+                rb[c] = base + 2 * (G::OFF + 16 * sv + 32 * c + 8 * g);
+            }
+        }
+        // D = 2: sample s of a 128-sample group at 64 (s >> 5) + 16 (((s >> 3) & 3) ^ ((s >> 6) & 3))
+        // + 2 (s & 7); group k adds 256 k and flips unit bit 1 when k is odd
+        wb0 = D == 4   ? base + 128 * (lane >> 5) + 4 * (lane & 3) + 16 * ((lane >> 2) & 7)
+              : D == 2 ? base + 64 * (lane >> 4) + 4 * (lane & 3) + 16 * (((lane >> 2) & 3) ^ (lane >> 5))
+                       : base + 4 * lane;
+    };
 
     // ---- the wave's tile stream ----
     // Units (runs of seg_tiles tiles of one channel) are dealt to waves either in per-
@@ -416,7 +441,7 @@ void fir_mxh_kernel(MxhParams p) {
     // the input) iff t < ftiles, and its outputs are whole 256-blocks iff t CS + j < oblk.
     struct Cur {
         int u, t, ch, tu, nt;
-        bool ok;
+        int ok;  // (an int: the struct has no padding bytes to copy around)
     };
     const int units = (int)p.units, spc = (int)p.spc, segt = (int)p.seg_tiles, tpc = (int)p.tpc;
     const int ust = p.blocked ? kWaves : (int)nwaves;
@@ -538,22 +563,45 @@ void fir_mxh_kernel(MxhParams p) {
     int nf_tiles = 0;  // tiles whose window held inf / NaN (wave-uniform)
     seek(cm, first_unit);
     if (cm.ok) {
+        // Ramp: the first sample loads go out before anything else, so the fragment table loads
+        // and the address setup run under their latency; tile 1's loads are issued group by group
+        // while tile 0 is staged (as in the body), not after the whole staging loop.
         Raw nx[NG], hr[NH];
         load_hist(hr, cm);
         load_tile(nx, cm);
+        ramp_setup();
+        st = cm;
+        adv(st);
+        const bool st_run = st.ok && st.t == 0;  // tile 1 opens a run: its history is reloaded
         int s_cur = window_scale(nx, hr);
         {
             const float sc = exp2i(s_cur);
 #pragma unroll
             for (int k = 0; k < NH; ++k) put(hist_addr(k), hr[k], sc);
+            if (st.ok && tile_fast(st)) {
+                if (st_run) load_hist(hr, st);
+                const long j1 = tile_j0(st);
+                Raw keep[NH];  // tile 0's tail: tile 1's history when it continues the run
 #pragma unroll
-            for (int k = 0; k < NG; ++k) put(new_addr(k), nx[k], sc);
+                for (int k = 0; k < NG; ++k) {
+                    put(new_addr(k), nx[k], sc);
+                    if (k >= NG - NH) keep[k - (NG - NH)] = nx[k];
+                    nx[k] = ldx(st, j1 + 128 * k + 2 * lane, std::true_type());
+                }
+                if (!st_run) {
+                    Raw tile[NG];
+#pragma unroll
+                    for (int k = 0; k < NG; ++k) tile[k] = keep[k < NG - NH ? 0 : k - (NG - NH)];
+                    roll_hist(hr, tile);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < NG; ++k) put(new_addr(k), nx[k], sc);
+                if (st_run) load_hist(hr, st);
+                else roll_hist(hr, nx);
+                if (st.ok) load_tile(nx, st);
+            }
         }
-        st = cm;
-        adv(st);
-        if (st.ok && st.t == 0) load_hist(hr, st);
-        else roll_hist(hr, nx);
-        if (st.ok) load_tile(nx, st);
         ld = st;
         adv(ld);
 
@@ -791,9 +839,35 @@ int fir_mxh_supported(const FirParams& fp) {
     return 1;
 }
 
+size_t fir_mxh_frag_bytes(int K, int D) {
+    const int NCH = K >= 1 ? mxh_nch(K, D) : 0;
+    return (size_t)D * 2 * NCH * 64 * sizeof(u32x4);
+}
+
+int fir_mxh_frag_build(const float* d_taps, int K, int D, int tap_scale_exp, void* d_frags,
+                       hipStream_t s) {
+    const int NCH = K >= 1 ? mxh_nch(K, D) : 0;
+    if (NCH == 0 || !d_taps || !d_frags) return SDRGPU_ERR_UNSUPPORTED;
+#define SDRGPU_MXH_FRAGS(CC, DD)                                                               \
+    if (D == DD && NCH == CC) {                                                                \
+        hipLaunchKernelGGL((tap_frag_kernel<CC, DD>), dim3(DD), dim3(64), 0, s, d_taps, K,     \
+                           tap_scale_exp, static_cast<u32x4*>(d_frags));                       \
+        SDRGPU_LAUNCH_CHECK();                                                                 \
+        return SDRGPU_OK;                                                                      \
+    }
+    SDRGPU_MXH_FRAGS(10, 4)
+    SDRGPU_MXH_FRAGS(6, 4)
+    SDRGPU_MXH_FRAGS(9, 1)
+    SDRGPU_MXH_FRAGS(5, 1)
+    SDRGPU_MXH_FRAGS(9, 2)
+    SDRGPU_MXH_FRAGS(5, 2)
+#undef SDRGPU_MXH_FRAGS
+    return SDRGPU_ERR_UNSUPPORTED;
+}
+
 int fir_mxh_launch(const FirParams& fp, const float* d_taps, int tap_scale_exp,
-                   const void* d_dummy, int cus, hipStream_t s) {
-    if (!fir_mxh_supported(fp) || !d_dummy) return SDRGPU_ERR_UNSUPPORTED;
+                   const void* d_frags, const void* d_dummy, int cus, hipStream_t s) {
+    if (!fir_mxh_supported(fp) || !d_dummy || !d_frags) return SDRGPU_ERR_UNSUPPORTED;
     const int D = fp.D;
     const int NCH = mxh_nch(fp.K, D);
     MxhParams p;
@@ -810,6 +884,7 @@ int fir_mxh_launch(const FirParams& fp, const float* d_taps, int tap_scale_exp,
     p.delta = (int)(D - 1 - fp.i0);
     p.sh = tap_scale_exp;
     p.taps = d_taps;
+    p.frags = static_cast<const u32x4*>(d_frags) + (size_t)p.delta * (2 * NCH * 64);
     p.out = static_cast<float2*>(fp.out);
     p.ld_out = fp.ld_out;
     p.vec_out = ((reinterpret_cast<uintptr_t>(fp.out) & 15) == 0 &&
@@ -817,7 +892,7 @@ int fir_mxh_launch(const FirParams& fp, const float* d_taps, int tap_scale_exp,
                     ? 1
                     : 0;
     const long nch = fp.nch;
-    const int cs = D == 1 ? kCs1 : (D == 2 ? kCs2 : 1);
+    const int cs = cs_of(D);
     p.tpc = ceil_div(std::max(0L, fp.n_out), 256L * cs);
     const long W = (long)kWaves * cus;
     // D = 4: runs of kRunTiles tiles (c64: grid-strided; u8: per-CU blocks, round 2: 0.516-0.525

@@ -41,6 +41,7 @@ void FirPaths::release() {
     DeviceGuard g(device);
     if (mx.d_taps) (void)hipFree(mx.d_taps);
     if (mx.d_dummy) (void)hipFree(mx.d_dummy);
+    if (mx.d_frags) (void)hipFree(mx.d_frags);
     mx = Mx();
     mx_tried = false;
     if (os_state) fir_os_release(os_state);
@@ -56,8 +57,10 @@ int FirPaths::set_algorithm(int a) {
     return SDRGPU_OK;
 }
 
-// Natural-order device taps, the zeroed dummy tile and the tap scale; tried once per handle.
-int FirPaths::mx_prepare() {
+// Natural-order device taps, the zeroed dummy tile, the tap scale and fir_mxh's tap fragment table
+// (every decimation phase, built from the taps just uploaded: the one place d_taps is written);
+// tried once per handle, on the stream of the block that needs it first.
+int FirPaths::mx_prepare(hipStream_t s) {
     if (mx_tried) return mx_status;
     mx_tried = true;
     const float* h = reinterpret_cast<const float*>(taps.data());
@@ -77,7 +80,15 @@ int FirPaths::mx_prepare() {
                     hipMemcpy(mx.d_taps, h, sizeof(float) * K, hipMemcpyHostToDevice) == hipSuccess &&
                     hipMalloc(&mx.d_dummy, fir_mxh_dummy_bytes()) == hipSuccess &&
                     hipMemset(mx.d_dummy, 0, fir_mxh_dummy_bytes()) == hipSuccess;
-    return mx_status = ok ? SDRGPU_OK : SDRGPU_ERR_NOMEM;
+    if (!ok) return mx_status = SDRGPU_ERR_NOMEM;
+    if (const size_t fb = fir_mxh_frag_bytes(K, D)) {
+        if (hipMalloc(&mx.d_frags, fb) != hipSuccess) return mx_status = SDRGPU_ERR_NOMEM;
+        if (int st = fir_mxh_frag_build(mx.d_taps, K, D, mx.tap_scale_exp, mx.d_frags, s))
+            return mx_status = st;
+        // the table outlives this stream's ordering (set_stream): complete before the first use
+        if (hipStreamSynchronize(s) != hipSuccess) return mx_status = SDRGPU_ERR_DEVICE;
+    }
+    return mx_status = SDRGPU_OK;
 }
 
 int FirPaths::launch(FirParams& p, hipStream_t s, int* ran_algo, int* kernel) {
@@ -88,7 +99,7 @@ int FirPaths::launch(FirParams& p, hipStream_t s, int* ran_algo, int* kernel) {
         if (status == SDRGPU_OK) *ran_algo = a, *kernel = k | conv;
         return status;
     };
-    if (try_mx && (st = mx_prepare())) return st;
+    if (try_mx && (st = mx_prepare(s))) return st;
 
     if (try_mx && p.sample_kind == SDRGPU_CU8) {
         // 1. fused u8 on int8 (16-byte aligned channels), 2. fused u8 on fp16 (4-byte aligned)
@@ -97,7 +108,7 @@ int FirPaths::launch(FirParams& p, hipStream_t s, int* ran_algo, int* kernel) {
                        fir_mxi_launch(p, mx.d_taps, mx.tap_scale_exp, mx.d_dummy, mx.cus, s));
         if (fir_mxh_supported(p))
             return ran(SDRGPU_FIR_MATRIX, SDRGPU_FIR_KERNEL_FP16,
-                       fir_mxh_launch(p, mx.d_taps, mx.tap_scale_exp, mx.d_dummy, mx.cus, s));
+                       fir_mxh_launch(p, mx.d_taps, mx.tap_scale_exp, mx.d_frags, mx.d_dummy, mx.cus, s));
     }
     if (p.sample_kind == SDRGPU_CU8) {
         // 3. no fused kernel for this block: convert it to c64 (RtlTcpSignal::next), dense rows,
@@ -114,7 +125,7 @@ int FirPaths::launch(FirParams& p, hipStream_t s, int* ran_algo, int* kernel) {
         // a block neither takes (unaligned channels) goes on down the list
         if (fir_mxh_supported(p))
             return ran(SDRGPU_FIR_MATRIX, SDRGPU_FIR_KERNEL_FP16,
-                       fir_mxh_launch(p, mx.d_taps, mx.tap_scale_exp, mx.d_dummy, mx.cus, s));
+                       fir_mxh_launch(p, mx.d_taps, mx.tap_scale_exp, mx.d_frags, mx.d_dummy, mx.cus, s));
         if (fir_mx3_supported(p))
             return ran(SDRGPU_FIR_MATRIX, SDRGPU_FIR_KERNEL_BF16X3,
                        fir_mx3_launch(p, mx.d_taps, mx.cus, s));

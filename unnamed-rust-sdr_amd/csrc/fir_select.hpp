@@ -48,6 +48,7 @@ private:
     struct Mx {
         float* d_taps = nullptr;  // natural order, K f32
         void* d_dummy = nullptr;  // zeroed target of the clamped prefetches (fir_mxh_dummy_bytes)
+        void* d_frags = nullptr;  // fir_mxh's tap fragments of every phase (fir_mxh_frag_bytes; may be none)
         int tap_scale_exp = 0;    // 15 - exponent(max |h|)
         bool taps_finite = true;  // fir_mxi takes integer taps: finite ones only
         int cus = 256;
@@ -60,7 +61,7 @@ private:
 
     bool mx_shape_ok() const;
     bool os_shape_ok() const;
-    int mx_prepare();
+    int mx_prepare(hipStream_t s);
 };
 
 }  // namespace sdrgpu
