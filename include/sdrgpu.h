@@ -18,6 +18,18 @@
  * concurrently; a handle may migrate between threads.  Each handle owns one HIP stream
  * (or uses one set with *_set_stream).
  *
+ * Streams: *_set_stream(h, s) makes the handle enqueue on the external stream s (NULL: on
+ * its own stream again), e.g. another handle's (*_get_stream), so that a chain of *_dev calls
+ * needs no host round trip between its stages.  It may be called at any time, also with
+ * work in flight: everything the handle enqueued before the call completes before anything
+ * it enqueues after it.  That ordering is made on the device (an event on the old stream
+ * that the new one waits for); the call does not block the host.  *_sync waits for the
+ * handle's current stream and therefore, by that ordering, for all of the handle's work.
+ * An external stream must stay alive until the handle has been switched away from it or
+ * destroyed.  A clone gets a stream of its own, whatever stream its source is on.
+ * *_set_stream returns SDRGPU_ERR_DEVICE (sdrgpu_src_set_stream: SDRGPU_SRC_ERR_BAD_STATE)
+ * when the ordering could not be enqueued; the handle then stays on its previous stream.
+ *
  * Buffers: the plain functions take HOST pointers and are synchronous.  The *_dev
  * variants take DEVICE pointers (on the handle's device), enqueue on the handle's stream
  * and return immediately; call *_sync or synchronise the stream before reading.

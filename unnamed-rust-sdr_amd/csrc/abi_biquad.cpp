@@ -140,8 +140,9 @@ int sdrgpu_biquad_coefs(const sdrgpu_biquad* h, float* coefs5) {
 
 int sdrgpu_biquad_set_stream(sdrgpu_biquad* h, void* s) {
     if (!h) return SDRGPU_ERR_INVALID;
-    h->stream.set(s);
-    return SDRGPU_OK;
+    DeviceGuard g(h->device);
+    if (!g.ok()) return SDRGPU_ERR_DEVICE;
+    return h->stream.set(s);
 }
 
 int sdrgpu_biquad_get_stream(const sdrgpu_biquad* h, void** s) {

@@ -56,14 +56,30 @@ struct DevBuf {
 struct StreamSlot {
     hipStream_t own = nullptr;
     hipStream_t cur = nullptr;
+    hipEvent_t switched = nullptr;  // created by the first set() that changes the stream
     int create() {
         if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess)
             return SDRGPU_ERR_DEVICE;
         cur = own;
         return SDRGPU_OK;
     }
-    void set(void* s) { cur = s ? static_cast<hipStream_t>(s) : own; }
+    // What a handle carries between blocks (history, filter state, scratch) is written by the
+    // previous block on the old stream and read by the next one on the new stream, so the new
+    // stream waits, on the device, for everything enqueued on the old one so far.  The host does
+    // not wait.  Call under the handle's DeviceGuard.
+    int set(void* s) {
+        const hipStream_t to = s ? static_cast<hipStream_t>(s) : own;
+        if (to == cur) return SDRGPU_OK;
+        if (!switched)
+            SDRGPU_HIP_TRY(hipEventCreateWithFlags(&switched, hipEventDisableTiming));
+        SDRGPU_HIP_TRY(hipEventRecord(switched, cur));
+        SDRGPU_HIP_TRY(hipStreamWaitEvent(to, switched, 0));
+        cur = to;
+        return SDRGPU_OK;
+    }
     void destroy() {
+        if (switched) (void)hipEventDestroy(switched);
+        switched = nullptr;
         if (own) (void)hipStreamDestroy(own);
         own = cur = nullptr;
     }

@@ -93,8 +93,9 @@ int sdrgpu_fft_plan(int device, size_t n, sdrgpu_fft** out) {
 
 int sdrgpu_fft_set_stream(sdrgpu_fft* h, void* s) {
     if (!h) return SDRGPU_ERR_INVALID;
-    h->stream.set(s);
-    return SDRGPU_OK;
+    DeviceGuard g(h->device);
+    if (!g.ok()) return SDRGPU_ERR_DEVICE;
+    return h->stream.set(s);
 }
 
 int sdrgpu_fft_get_stream(const sdrgpu_fft* h, void** s) {
@@ -228,8 +229,9 @@ int sdrgpu_stft_create(int device, size_t n, size_t hop, sdrgpu_stft** out) {
 
 int sdrgpu_stft_set_stream(sdrgpu_stft* h, void* s) {
     if (!h) return SDRGPU_ERR_INVALID;
-    h->fft.stream.set(s);
-    return SDRGPU_OK;
+    DeviceGuard g(h->fft.device);
+    if (!g.ok()) return SDRGPU_ERR_DEVICE;
+    return h->fft.stream.set(s);
 }
 
 int sdrgpu_stft_get_stream(const sdrgpu_stft* h, void** s) {

@@ -271,8 +271,9 @@ int set_algorithm(FirCore* c, int algo) {
 
 int set_stream(FirCore* c, void* s) {
     if (!c) return SDRGPU_ERR_INVALID;
-    c->stream.set(s);
-    return SDRGPU_OK;
+    DeviceGuard g(c->device);
+    if (!g.ok()) return SDRGPU_ERR_DEVICE;
+    return c->stream.set(s);
 }
 
 int get_stream(const FirCore* c, void** s) {

@@ -262,8 +262,9 @@ int sdrgpu_pll_last_phase_ms(sdrgpu_pll* h, float* pass1, float* rerun, float* w
 
 int sdrgpu_pll_set_stream(sdrgpu_pll* h, void* s) {
     if (!h) return SDRGPU_ERR_INVALID;
-    h->stream.set(s);
-    return SDRGPU_OK;
+    DeviceGuard g(h->device);
+    if (!g.ok()) return SDRGPU_ERR_DEVICE;
+    return h->stream.set(s);
 }
 
 int sdrgpu_pll_get_stream(const sdrgpu_pll* h, void** s) {

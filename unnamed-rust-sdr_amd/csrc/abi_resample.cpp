@@ -727,7 +727,8 @@ int sdrgpu_src_set_ratio(sdrgpu_src_state* s, double new_ratio) {
 
 int sdrgpu_src_set_stream(sdrgpu_src_state* s, void* hip_stream) {
     if (!s) return SDRGPU_SRC_ERR_BAD_STATE;
-    s->stream.set(hip_stream);
+    DeviceGuard g(s->device);
+    if (!g.ok() || s->stream.set(hip_stream) != SDRGPU_OK) return SDRGPU_SRC_ERR_BAD_STATE;
     return 0;
 }
 

@@ -61,7 +61,11 @@ class DeviceBuffer:
                                     D2D), "copy_from")
 
     def fill_zero(self):
-        check(lib().sdrgpu_dev_memset(self.device, self.ptr, 0, self.nbytes), "memset")
+        self.fill(0)
+
+    def fill(self, value: int):
+        """Set every byte to `value` (0xFF reads back as NaN floats)."""
+        check(lib().sdrgpu_dev_memset(self.device, self.ptr, value, self.nbytes), "memset")
 
     def free(self):
         if self.ptr:

@@ -58,6 +58,9 @@ class FftPlan:
         except Exception:
             pass
 
+    def set_stream(self, stream_ptr: Optional[int]):
+        check(lib().sdrgpu_fft_set_stream(self._h, stream_ptr), "sdrgpu_fft_set_stream")
+
     def stream(self) -> int:
         s = ctypes.c_void_p()
         check(lib().sdrgpu_fft_get_stream(self._h, ctypes.byref(s)), "get_stream")
@@ -144,6 +147,9 @@ class Stft:
             self.close()
         except Exception:
             pass
+
+    def set_stream(self, stream_ptr: Optional[int]):
+        check(lib().sdrgpu_stft_set_stream(self._h, stream_ptr), "sdrgpu_stft_set_stream")
 
     def stream(self) -> int:
         s = ctypes.c_void_p()

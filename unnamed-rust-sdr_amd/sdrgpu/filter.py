@@ -392,6 +392,9 @@ class Biquad:
     def reset(self):
         check(lib().sdrgpu_biquad_reset(self._h), "sdrgpu_biquad_reset")
 
+    def set_stream(self, stream_ptr: Optional[int]):
+        check(lib().sdrgpu_biquad_set_stream(self._h, stream_ptr), "sdrgpu_biquad_set_stream")
+
     def stream(self) -> int:
         s = ctypes.c_void_p()
         check(lib().sdrgpu_biquad_get_stream(self._h, ctypes.byref(s)), "get_stream")

@@ -136,6 +136,9 @@ class SampleRate:
         Error.result(lib().sdrgpu_src_process_dev(self.h, ctypes.byref(d)))
         return d.input_frames_used, d.output_frames_gen
 
+    def set_stream(self, stream_ptr):
+        Error.result(lib().sdrgpu_src_set_stream(self.h, stream_ptr))
+
     def stream(self) -> int:
         p = c_void_p()
         Error.result(lib().sdrgpu_src_get_stream(self.h, ctypes.byref(p)))
