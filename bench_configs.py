@@ -15,6 +15,8 @@ per config:
       8192 channels x 2^16 c64 (1024 per GPU at 8 GPUs)
   c2u8  configs[1] fed from rtl_tcp u8 IQ:    2 B in + 2 B out / sample
       (v-128)/128 fused into the FIR load, 2^28 samples
+  chan  polyphase channelizer, 1024 channels, 8192 taps,    8 B in + 8 B out / sample (u8 leg:
+      2^26 c64 samples (not part of `all`)                  2 B in + 8 B out), HBM roof
 
 Multi-GPU (c5): `python -m torch.distributed.run --nproc-per-node N bench_configs.py
 --config c5`; each rank filters its resident channel shard (weak: 8192/N channels per rank
@@ -40,7 +42,7 @@ HBM_GBS = 8000.0
 
 def parse():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="all", choices=["c1", "c3", "c4", "c5", "c2u8", "c2host", "c2pinned", "src", "ex", "fm", "all"])
+    ap.add_argument("--config", default="all", choices=["c1", "c3", "c4", "c5", "c2u8", "c2host", "c2pinned", "src", "ex", "fm", "chan", "all"])
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--c3-log2n", type=int, default=28)
@@ -52,6 +54,9 @@ def parse():
     ap.add_argument("--fm-seconds", type=float, default=10.0, help="seconds of air through the fm chain")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true", help="timing-only ablation builds: skip the c3 / c5 spot checks")
+    ap.add_argument("--chan-log2n", type=int, default=26)
+    ap.add_argument("--no-fir-route", action="store_true",
+                    help="chan only: skip timing the one-Fir-per-channel route")
     ap.add_argument("--gpus", type=int, default=1,
                     help="c5 only: run as this many ranks (self-launched, one process per GPU)")
     return ap.parse_args()
@@ -606,6 +611,111 @@ def bench_fm(args):
     return res
 
 
+# ------------------------------------------------------------------------------ chan
+def chan_ref_f64(h, M, seg):
+    """The channelizer's polyphase form in f64: seg holds (P-1)*M samples of
+    history, then whole frames; returns (M, frames)."""
+    P = -(-h.size // M)
+    hp = np.zeros(P * M)
+    hp[:h.size] = h
+    fr = np.asarray(seg, np.complex128).reshape(-1, M)
+    nf = fr.shape[0] - (P - 1)
+    v = sum(hp[q * M + M - 1 - np.arange(M)] * fr[P - 1 - q:P - 1 - q + nf] for q in range(P))
+    return np.fft.fft(v, axis=1).T
+
+
+def bench_chan(args):
+    """Polyphase channelizer (sdrgpu.Channelizer): one stream of 2^26 samples into 1024 channel
+    rows, prototype firwin(8192, 1/1024), c64 input (8 B in + 8 B out per input sample) and
+    rtl_tcp u8 input (2 B in + 8 B out); inputs resident, event-timed on the handle's stream.
+    Spot check of the timed outputs (the last step's): 8 frames at the start, in the middle
+    and at the end, all 1024 channels, against the f64 polyphase form (the oracle's own f32 sum
+    over 8192 complex taps is 1.08e-5 of RMS from f64, outside the tolerance it would check).
+    The handle streams, so the history entering a step is the end of the step before it.
+    fir_route: the only route without the channelizer -- one sdrgpu_fir per channel with c64
+    taps h[n] exp(2j pi k (n+1) / M) and decimation M over the same input -- timed for 8 handles
+    on one stream and scaled to 1024."""
+    import scipy.signal as ss
+    import sdrgpu
+    from sdrgpu.device import DeviceBuffer, synchronize
+    M, n = 1024, 1 << args.chan_log2n
+    L, n_out = 8 * M, n // M
+    P = L // M
+    h = ss.firwin(L, 1.0 / M).astype(np.float32)
+    pat_n = min(n, 1 << 22)
+    first_call = args.steps + args.warmup == 1
+    y = DeviceBuffer.empty(M * n_out)
+    res = {"config": f"chan: polyphase channelizer, {M} channels, firwin({L}, 1/{M}) prototype, "
+                     f"2^{args.chan_log2n} samples -> {M} x {n_out} c64",
+           "metric": "complex Msamples/s (input)"}
+
+    def check(pat):
+        worst = 0.0
+        for m0 in (0, n_out // 2 + 3, n_out - 8):
+            g = np.arange((m0 + 1 - P) * M, (m0 + 8) * M)
+            seg = pat[g % pat_n]
+            if first_call:
+                seg = np.where(g >= 0, seg, 0)
+            ref = chan_ref_f64(h, M, seg)
+            got = np.stack([y.download(8, offset_bytes=8 * (k * n_out + m0)) for k in range(M)])
+            worst = max(worst, float(np.abs(got - ref).max() / np.sqrt(np.mean(np.abs(ref) ** 2))))
+        assert worst <= 1e-5 or args.no_check, worst
+        return worst
+
+    # c64 leg
+    ch = sdrgpu.Channelizer(h, M)
+    x = DeviceBuffer.empty(n)
+    fill(x, n, 31)
+
+    def step():
+        assert ch.process_dev(x.ptr, n, y.ptr, n_out) == n_out
+
+    wall, ms = time_events(step, ch.stream(), args.steps, args.warmup, lambda: (ch.sync(), synchronize()))
+    res.update({"value": round(n / (ms * 1e-3) / 1e6, 1), "roofline": roof(16, n, ms),
+                "wall_ms_per_step": round(wall * 1e3, 3),
+                "spot_check_max_over_rms": check(cplx_pattern(pat_n, 31))})
+    if not args.no_fir_route:
+        nh = 8
+        k_taps = [(h.astype(np.float64) * np.exp(2j * np.pi * k * (np.arange(L) + 1.0) / M)).astype(np.complex64)
+                  for k in range(nh)]
+        firs = [sdrgpu.filter.Fir(t, decim=M, sample_kind=sdrgpu.C64).design() for t in k_taps]
+        for f in firs[1:]:
+            f.set_stream(firs[0].stream())
+        outs = [DeviceBuffer.empty(n_out) for _ in firs]
+
+        def fir_step():
+            for f, o in zip(firs, outs):
+                assert f.process_dev(x.ptr, n, o.ptr, n_out) == n_out
+
+        _, ms8 = time_events(fir_step, firs[0].stream(), args.steps, args.warmup,
+                             lambda: (firs[0].sync(), synchronize()))
+        a, b = outs[nh - 1].download(), y.download(n_out, offset_bytes=8 * (nh - 1) * n_out)
+        res["fir_route"] = {"handles_timed": nh, "ms_timed": round(ms8, 3),
+                            "ms_scaled_to_all_channels": round(ms8 * M / nh, 1), "scaled": True,
+                            "algorithm": firs[0].last_algorithm(),
+                            "ratio_to_channelizer": round(ms8 * M / nh / ms, 1),
+                            "channel_vs_channelizer_max_over_rms":
+                                float(np.abs(a - b).max() / np.sqrt(np.mean(np.abs(b) ** 2)))}
+        del firs, outs
+    del x
+    # rtl_tcp u8 leg
+    ch8 = sdrgpu.Channelizer(h, M, sample_kind=sdrgpu.CU8)
+    pat8 = np.random.default_rng(32).integers(0, 256, size=2 * pat_n, dtype=np.uint8)
+    x8 = DeviceBuffer.empty(2 * n, np.uint8)
+    for off in range(0, 2 * n, pat8.size):
+        x8.upload(pat8, offset_bytes=off)
+
+    def step8():
+        assert ch8.process_dev(x8.ptr, n, y.ptr, n_out) == n_out
+
+    wall8, ms8 = time_events(step8, ch8.stream(), args.steps, args.warmup, lambda: (ch8.sync(), synchronize()))
+    p8 = (pat8.astype(np.float64) - 128.0) / 128.0
+    res["cu8"] = {"value": round(n / (ms8 * 1e-3) / 1e6, 1), "roofline": roof(10, n, ms8),
+                  "wall_ms_per_step": round(wall8 * 1e3, 3),
+                  "spot_check_max_over_rms": check(p8[0::2] + 1j * p8[1::2])}
+    return res
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -617,7 +727,7 @@ def main():
     for c in todo:
         r = {"c1": bench_c1, "c3": bench_c3, "c4": bench_c4, "c5": bench_c5, "c2u8": bench_c2u8,
              "c2host": bench_c2host, "c2pinned": bench_c2pinned, "src": bench_src, "ex": bench_ex,
-             "fm": bench_fm}[c](args)
+             "fm": bench_fm, "chan": bench_chan}[c](args)
         for line in (r if isinstance(r, list) else [r]):
             if line is not None:
                 print(json.dumps(line), flush=True)

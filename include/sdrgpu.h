@@ -162,8 +162,8 @@ int sdrgpu_fir_process(sdrgpu_fir* h, const void* in, size_t n_in, void* out,
 /* DEVICE pointers, enqueued on the handle's stream.  d_out may overlap d_in (in place, or
  * shifted): the handle then filters a device copy of the input, so the results are those of an
  * out-of-place call (the kernels store output tiles while other workgroups still read the
- * input under them).  The same holds for sdrgpu_firbank_process_dev, sdrgpu_fft_exec_dev,
- * sdrgpu_rfft_exec_dev and sdrgpu_stft_process_dev. */
+ * input under them).  The same holds for sdrgpu_firbank_process_dev, sdrgpu_chan_process_dev,
+ * sdrgpu_fft_exec_dev, sdrgpu_rfft_exec_dev and sdrgpu_stft_process_dev. */
 int sdrgpu_fir_process_dev(sdrgpu_fir* h, const void* d_in, size_t n_in, void* d_out,
                            size_t out_cap, size_t* n_out);
 /* HOST pointers, asynchronous (the Block adapter's producer/consumer split,
@@ -205,6 +205,46 @@ int sdrgpu_firbank_last_kernel(const sdrgpu_firbank* h, int* kernel);
 int sdrgpu_firbank_reset(sdrgpu_firbank* h);
 int sdrgpu_firbank_clone(const sdrgpu_firbank* h, sdrgpu_firbank** out);
 void sdrgpu_firbank_destroy(sdrgpu_firbank* h);
+
+/* Polyphase channelizer: one wideband stream into nch = M channel rows.
+ * Replaces M chains signal.filter(c_k).decimate(rate / M), k = 0..M-1, with the complex taps
+ * c_k[n] = taps[n] * exp(+j*2*pi*k*(n+1)/M) (Fir with Complex taps, src/filter/fir.rs:23-32;
+ * Decimate keeps stream indices M-1, 2M-1, ..., src/signal/adapters/mod.rs:30-37):
+ *   y_k[m] = sum_{n<ntaps} taps[n] * exp(+j*2*pi*k*(n+1)/M) * x[m*M + M-1 - n],  x[<0] = 0,
+ * i.e. mix down by k*rate/M, low-pass with the real prototype `taps`, keep every M-th sample;
+ * channel k is the band centred at +k*rate/M (k > M/2: a negative frequency).  Computed in the
+ * polyphase form (one real x complex MAC per tap per input sample, then an unscaled forward
+ * M-point DFT per output frame), within the parity tolerance of the chains.
+ * sample_kind: SDRGPU_C64, or SDRGPU_CU8 (rtl_tcp bytes, (v-128)/128 fused into the load);
+ * SDRGPU_F32 is SDRGPU_ERR_UNSUPPORTED.  Outputs are C64.  nch: a power of two, 2..4096, and
+ * ceil(ntaps / nch) <= 64; other sizes are SDRGPU_ERR_UNSUPPORTED.
+ * Output layout, channel-major: channel k's m-th output of this call goes to out + k*ld_out + m
+ * (ld_out in samples, ld_out < n_out: SDRGPU_ERR_OUTPUT_CAP) -- what sdrgpu_firbank_process_dev
+ * and sdrgpu_pll_process_dev read with ld_in = ld_out.  *n_out is per channel.
+ * State (the last ceil(ntaps/M)*M - 1 samples, the stream's sample count) is kept on the device
+ * and carries across calls: n_out = floor((seen + n_in)/M) - floor(seen/M), and any partition
+ * of a stream into blocks -- 1-sample blocks and blocks that produce nothing included -- gives
+ * bit-identical outputs.  d_out may overlap d_in (see sdrgpu_fir_process_dev).
+ * Non-finite samples: parity with the reference's sum is NOT promised here.  The taps are
+ * zero-padded to a multiple of M and every channel of a frame sums all its branches, so an
+ * inf / NaN sample makes every channel of every frame whose ceil(ntaps/M)*M-sample window
+ * holds it non-finite (the chains: only the outputs whose ntaps-sample window holds it);
+ * frames whose window does not hold it are unaffected. */
+typedef struct sdrgpu_chan sdrgpu_chan;
+
+int sdrgpu_chan_create(int device, int sample_kind, const float* taps, size_t ntaps, size_t nch,
+                       sdrgpu_chan** out);
+int sdrgpu_chan_set_stream(sdrgpu_chan* h, void* hip_stream);
+int sdrgpu_chan_get_stream(const sdrgpu_chan* h, void** hip_stream);
+int sdrgpu_chan_output_len(const sdrgpu_chan* h, size_t n_in, size_t* n_out);
+int sdrgpu_chan_process(sdrgpu_chan* h, const void* in, size_t n_in, void* out, size_t ld_out,
+                        size_t* n_out);
+int sdrgpu_chan_process_dev(sdrgpu_chan* h, const void* d_in, size_t n_in, void* d_out,
+                            size_t ld_out, size_t* n_out);
+int sdrgpu_chan_sync(sdrgpu_chan* h);
+int sdrgpu_chan_reset(sdrgpu_chan* h);
+int sdrgpu_chan_clone(const sdrgpu_chan* h, sdrgpu_chan** out);
+void sdrgpu_chan_destroy(sdrgpu_chan* h);
 
 /* =====================================================================================
  * FFT.

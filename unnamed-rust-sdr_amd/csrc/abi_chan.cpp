@@ -1,0 +1,237 @@
+// abi_chan.cpp -- C ABI of the polyphase channelizer (sdrgpu_chan, include/sdrgpu.h).
+//
+// Replaces M chains signal.filter(c_k).decimate(rate / M) (Fir with Complex taps, reference
+// src/filter/fir.rs:23-32; Decimate, src/signal/adapters/mod.rs:30-37) by one handle.  Stream
+// state -- the last P*M - 1 samples, of which seen % M are not framed yet, and the sample count
+// -- is carried on the device across calls, so block partitioning never changes the outputs
+// (chan.hip computes every frame with the same arithmetic wherever it falls).
+#include <new>
+#include <vector>
+
+#include "abi_common.hpp"
+#include "chan_kernels.hpp"
+#include "fft_tile.hpp"
+
+using namespace sdrgpu;
+using namespace sdrgpu::detail;
+
+// taps per polyphase branch, P = ceil(ntaps / nch): the history is P*nch - 1 samples (2 MiB of
+// c64 at 4096 channels) and every frame reads P*nch samples
+static constexpr size_t kChanMaxP = 64;
+
+struct sdrgpu_chan {
+    int device = 0;
+    int sk = SDRGPU_C64;
+    int M = 2, P = 1;
+    std::vector<float> taps;               // as given (clone)
+    float* d_taps_pm = nullptr;            // P*M, polyphase-major (chan_kernels.hpp)
+    float2* d_tw = nullptr;
+    float2* d_hist[2] = {nullptr, nullptr};  // ping-pong, P*M - 1 samples each
+    int cur = 0;
+    unsigned long long seen = 0;           // stream samples consumed
+    StreamSlot stream;
+    DevBuf stage_in, stage_out, stage_alias;
+
+    size_t in_bytes() const { return kind_bytes(sk); }
+    size_t H() const { return (size_t)P * M - 1; }
+    size_t out_len(size_t n_in) const { return (size_t)((seen % (unsigned)M + n_in) / (unsigned)M); }
+
+    void free_all() {
+        DeviceGuard g(device);
+        if (d_taps_pm) (void)hipFree(d_taps_pm);
+        if (d_tw) (void)hipFree(d_tw);
+        for (auto& p : d_hist)
+            if (p) (void)hipFree(p);
+        d_taps_pm = nullptr;
+        d_tw = nullptr;
+        d_hist[0] = d_hist[1] = nullptr;
+        stage_in.release();
+        stage_out.release();
+        stage_alias.release();
+        stream.destroy();
+    }
+
+    int reset_state() {
+        DeviceGuard g(device);
+        if (!g.ok()) return SDRGPU_ERR_DEVICE;
+        seen = 0;
+        cur = 0;
+        SDRGPU_HIP_TRY(hipMemsetAsync(d_hist[0], 0, H() * sizeof(float2), stream.cur));
+        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
+        return SDRGPU_OK;
+    }
+
+    int init(int dev, int sample_kind, const float* h, size_t ntaps, size_t nch) {
+        if (!h || ntaps == 0 || nch == 0) return SDRGPU_ERR_INVALID;
+        if (sample_kind != SDRGPU_C64 && sample_kind != SDRGPU_CU8)
+            return sample_kind == SDRGPU_F32 ? SDRGPU_ERR_UNSUPPORTED : SDRGPU_ERR_INVALID;
+        if (!chan_size_ok(nch) || (ntaps + nch - 1) / nch > kChanMaxP) return SDRGPU_ERR_UNSUPPORTED;
+        int st = check_device(dev);
+        if (st) return st;
+        device = dev;
+        sk = sample_kind;
+        M = (int)nch;
+        P = (int)((ntaps + nch - 1) / nch);
+        taps.assign(h, h + ntaps);
+
+        DeviceGuard g(device);
+        if (!g.ok()) return SDRGPU_ERR_DEVICE;
+        if ((st = stream.create())) return st;
+        // taps_pm[q*M + r] = h[q*M + M-1-r]: lane r of a wave reads consecutive floats
+        std::vector<float> pm((size_t)P * M, 0.0f);
+        for (size_t n = 0; n < ntaps; ++n) pm[n / M * M + (M - 1 - n % M)] = h[n];
+        const std::vector<float2> tw = fftd::tile_twiddles();
+        SDRGPU_HIP_TRY(hipMalloc(&d_taps_pm, pm.size() * sizeof(float)));
+        SDRGPU_HIP_TRY(hipMemcpy(d_taps_pm, pm.data(), pm.size() * sizeof(float), hipMemcpyHostToDevice));
+        SDRGPU_HIP_TRY(hipMalloc(&d_tw, tw.size() * sizeof(float2)));
+        SDRGPU_HIP_TRY(hipMemcpy(d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
+        SDRGPU_HIP_TRY(hipMalloc(&d_hist[0], H() * sizeof(float2)));
+        SDRGPU_HIP_TRY(hipMalloc(&d_hist[1], H() * sizeof(float2)));
+        return reset_state();
+    }
+
+    // Enqueue one block (device pointers) on the current stream; ld_out >= out_len(n_in).
+    int run_dev(const void* d_in, size_t n_in, void* d_out, size_t ld_out) {
+        const size_t n_out = out_len(n_in);
+        if (n_in == 0) return SDRGPU_OK;
+        if (!d_in || (n_out > 0 && !d_out)) return SDRGPU_ERR_INVALID;
+        int st = unalias_input(stage_alias, d_in, n_in * in_bytes(), d_out,
+                               rows_span((size_t)M, ld_out, n_out, sizeof(float2)), stream.cur);
+        if (st) return st;
+        ChanArgs a{};
+        a.in = d_in;
+        a.n_in = (long)n_in;
+        a.hist = d_hist[cur];
+        a.hist_next = d_hist[cur ^ 1];
+        a.H = (long)H();
+        a.pend = (long)(seen % (unsigned)M);
+        a.nframes = (long)n_out;
+        a.P = P;
+        a.taps_pm = d_taps_pm;
+        a.tw = d_tw;
+        a.out = static_cast<float2*>(d_out);
+        a.ld_out = (long)ld_out;
+        if ((st = chan_launch(M, sk, a, stream.cur))) return st;
+        cur ^= 1;
+        seen += n_in;
+        return SDRGPU_OK;
+    }
+
+    int process_host(const void* in, size_t n_in, void* out, size_t ld_out) {
+        const size_t n_out = out_len(n_in);
+        if (n_in == 0) return SDRGPU_OK;
+        if (!in || (n_out && !out)) return SDRGPU_ERR_INVALID;
+        DeviceGuard g(device);
+        if (!g.ok()) return SDRGPU_ERR_DEVICE;
+        const size_t row = n_out * sizeof(float2);
+        int st;
+        if ((st = stage_in.ensure(n_in * in_bytes()))) return st;
+        if ((st = stage_out.ensure((size_t)M * (n_out ? n_out : 1) * sizeof(float2)))) return st;
+        SDRGPU_HIP_TRY(hipMemcpyAsync(stage_in.ptr, in, n_in * in_bytes(), hipMemcpyHostToDevice, stream.cur));
+        if ((st = run_dev(stage_in.ptr, n_in, stage_out.ptr, n_out))) return st;
+        if (n_out)
+            SDRGPU_HIP_TRY(hipMemcpy2DAsync(out, ld_out * sizeof(float2), stage_out.ptr, row, row,
+                                            (size_t)M, hipMemcpyDeviceToHost, stream.cur));
+        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
+        return SDRGPU_OK;
+    }
+
+    int clone_into(sdrgpu_chan* dst) const {
+        int st = dst->init(device, sk, taps.data(), taps.size(), (size_t)M);
+        if (st) return st;
+        DeviceGuard g(device);
+        dst->seen = seen;
+        SDRGPU_HIP_TRY(hipMemcpyAsync(dst->d_hist[0], d_hist[cur], H() * sizeof(float2),
+                                      hipMemcpyDeviceToDevice, stream.cur));
+        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
+        return SDRGPU_OK;
+    }
+};
+
+namespace {
+
+template <class Init>
+int make_handle(sdrgpu_chan** out, Init init) {
+    if (!out) return SDRGPU_ERR_INVALID;
+    *out = nullptr;
+    auto* h = new (std::nothrow) sdrgpu_chan();
+    if (!h) return SDRGPU_ERR_NOMEM;
+    const int st = init(h);
+    if (st) {
+        h->free_all();
+        delete h;
+        return st;
+    }
+    *out = h;
+    return SDRGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdrgpu_chan_create(int device, int sample_kind, const float* taps, size_t ntaps, size_t nch,
+                       sdrgpu_chan** out) {
+    return make_handle(out, [&](sdrgpu_chan* h) { return h->init(device, sample_kind, taps, ntaps, nch); });
+}
+
+int sdrgpu_chan_clone(const sdrgpu_chan* h, sdrgpu_chan** out) {
+    if (!h) return SDRGPU_ERR_INVALID;
+    return make_handle(out, [&](sdrgpu_chan* c) { return h->clone_into(c); });
+}
+
+void sdrgpu_chan_destroy(sdrgpu_chan* h) {
+    if (!h) return;
+    h->free_all();
+    delete h;
+}
+
+int sdrgpu_chan_set_stream(sdrgpu_chan* h, void* s) {
+    if (!h) return SDRGPU_ERR_INVALID;
+    DeviceGuard g(h->device);
+    if (!g.ok()) return SDRGPU_ERR_DEVICE;
+    return h->stream.set(s);
+}
+
+int sdrgpu_chan_get_stream(const sdrgpu_chan* h, void** s) {
+    if (!h || !s) return SDRGPU_ERR_INVALID;
+    *s = h->stream.cur;
+    return SDRGPU_OK;
+}
+
+int sdrgpu_chan_output_len(const sdrgpu_chan* h, size_t n_in, size_t* n_out) {
+    if (!h || !n_out) return SDRGPU_ERR_INVALID;
+    *n_out = h->out_len(n_in);
+    return SDRGPU_OK;
+}
+
+int sdrgpu_chan_process(sdrgpu_chan* h, const void* in, size_t n_in, void* out, size_t ld_out,
+                        size_t* n_out) {
+    if (!h) return SDRGPU_ERR_INVALID;
+    const size_t need = h->out_len(n_in);
+    if (n_out) *n_out = need;
+    if (ld_out < need) return SDRGPU_ERR_OUTPUT_CAP;
+    return h->process_host(in, n_in, out, ld_out);
+}
+
+int sdrgpu_chan_process_dev(sdrgpu_chan* h, const void* d_in, size_t n_in, void* d_out,
+                            size_t ld_out, size_t* n_out) {
+    if (!h) return SDRGPU_ERR_INVALID;
+    const size_t need = h->out_len(n_in);
+    if (n_out) *n_out = need;
+    if (ld_out < need) return SDRGPU_ERR_OUTPUT_CAP;
+    DeviceGuard g(h->device);
+    if (!g.ok()) return SDRGPU_ERR_DEVICE;
+    return h->run_dev(d_in, n_in, d_out, ld_out);
+}
+
+int sdrgpu_chan_sync(sdrgpu_chan* h) {
+    if (!h) return SDRGPU_ERR_INVALID;
+    DeviceGuard g(h->device);
+    SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
+    return SDRGPU_OK;
+}
+
+int sdrgpu_chan_reset(sdrgpu_chan* h) { return h ? h->reset_state() : SDRGPU_ERR_INVALID; }
+
+}  // extern "C"

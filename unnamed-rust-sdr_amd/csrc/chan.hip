@@ -1,0 +1,207 @@
+// chan.hip -- polyphase channelizer for gfx950: one wideband stream into M channel rows.
+//
+// Semantics: channel k is signal.filter(c_k).decimate(rate / M) with the complex taps
+// c_k[n] = h[n] exp(+2 pi i k (n+1) / M) (Fir with Complex taps, reference src/filter/fir.rs:23-32;
+// Decimate keeps stream indices M-1, 2M-1, ..., src/signal/adapters/mod.rs:30-37):
+//   y_k[m] = sum_{n<L} h[n] exp(+2 pi i k (n+1) / M) x[m M + M-1 - n],  x[<0] = 0.
+// With P = ceil(L / M), h zero-padded to P M and n = q M + M-1 - r the exponential is
+// exp(-2 pi i k r / M), so
+//   v_r[m] = sum_{q<P} h[q M + M-1 - r] x[(m - q) M + r]      one real x complex MAC per tap
+//   y_k[m] = sum_r v_r[m] exp(-2 pi i k r / M)                a forward M-point DFT per frame.
+//
+// Kernel (BLK lanes, 16 points per lane, one LDS tile of T = 16 BLK points per workgroup,
+// fft_tile.hpp): a workgroup owns F = T/M consecutive frames x M channels.  Tile point
+// p = f M + r of tap row q is stream sample g0 + p - q M, one T-sample window that slides back
+// by M per q, so every load of a wave is contiguous; the window is read from the history buffer
+// where it reaches in front of the block.  The sums go to LDS, tile_fft<M> transforms the F
+// frames in place, and the [frame][channel] tile is stored [channel][frame]: each channel row
+// receives its F frames as one contiguous run.  The workgroups after the tiles write the
+// history the next block reads.  Every frame is the same arithmetic on its P M samples in the
+// same order (q ascending, then the transform), whatever the block boundaries, the tile size
+// and the frame's place in its tile.
+// Tile size: 256 lanes / 4096 points below kChanBigMinM channels; from there on 1024 lanes /
+// 16384 points (136 KiB of LDS, one workgroup per CU), which makes a channel's run of frames
+// 128 B at M = 1024 instead of 32 B and reads (F + P - 1)/F = 1.44 instead of 2.75 times the
+// input at P = 8 (measured: DESIGN.md 3.4a).
+#include <algorithm>
+
+#include "chan_kernels.hpp"
+#include "fft_frames.hpp"
+#include "fft_tile.hpp"
+
+namespace sdrgpu {
+
+using namespace fftd;
+
+namespace {
+
+#ifndef SDRGPU_CHAN_BIG_MIN_M  // variant builds for the A/B of the two tile sizes
+#define SDRGPU_CHAN_BIG_MIN_M 1024
+#endif
+constexpr int kChanBigMinM = SDRGPU_CHAN_BIG_MIN_M;
+
+template <int M, int BLK>
+struct ChanTile {
+    static constexpr int T = 16 * BLK;  // points per tile
+    static constexpr int F = T / M;     // frames per tile
+    // [frame][channel] image read across frames by the store: 32 consecutive lanes (f fastest,
+    // then k) fall on 32 different 8-byte bank pairs
+    static constexpr int PITCH = M + (F >= 32 ? 1 : 32 / F);
+    static constexpr int LDS = F * PITCH > T + T / 16 ? F * PITCH : T + T / 16;  // float2
+};
+
+template <bool U8>
+__device__ __forceinline__ float2 block_sample(const void* in, long g) {
+    if constexpr (U8) return u8_sample(static_cast<const unsigned short*>(in)[g]);
+    else return static_cast<const float2*>(in)[g];
+}
+
+// sample g of the history followed by the block
+template <bool U8>
+__device__ __forceinline__ float2 stream_sample(const ChanArgs& a, long g) {
+    return g < 0 ? a.hist[a.H + g] : block_sample<U8>(a.in, g);
+}
+
+// tap row q of the tile: acc[i] += h[q M + r] x[b + p], p = t + BLK i, r = p % M; points at or
+// past npts (frames the block does not hold) take x = 0.
+template <int M, bool U8, int BLK>
+__device__ __forceinline__ void tap_row(const ChanArgs& a, const float* __restrict__ hq, long b,
+                                        int npts, float2 (&acc)[16]) {
+    const int t = threadIdx.x;
+    float2 x[16];
+    float h[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int p = t + BLK * i;
+        h[i] = hq[p % M];
+        x[i] = make_float2(0.f, 0.f);
+        if (p < npts) x[i] = stream_sample<U8>(a, b + p);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        acc[i].x = fmaf(h[i], x[i].x, acc[i].x);
+        acc[i].y = fmaf(h[i], x[i].y, acc[i].y);
+    }
+}
+
+template <int M, bool U8, int BLK>
+__global__ __launch_bounds__(BLK) void chan_tile_kernel(ChanArgs a) {
+    constexpr int F = ChanTile<M, BLK>::F, PITCH = ChanTile<M, BLK>::PITCH;
+    extern __shared__ float2 lds[];  // ChanTile::LDS
+    const int t = threadIdx.x;
+    if (blockIdx.x >= a.ntiles) {
+        // history carry: hist_next[j] = stream sample n_in - H + j
+        const long nb = gridDim.x - a.ntiles;
+        for (long j = (long)(blockIdx.x - a.ntiles) * BLK + t; j < a.H; j += nb * BLK)
+            a.hist_next[j] = stream_sample<U8>(a, a.n_in - a.H + j);
+        return;
+    }
+    const long f0 = (long)blockIdx.x * F;
+    const int nf = (int)min((long)F, a.nframes - f0);
+    const int npts = nf * M;
+    const long g0 = f0 * M - a.pend;  // stream sample of tile point 0 in tap row 0
+    float2 acc[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = make_float2(0.f, 0.f);
+    if constexpr (M >= BLK) {
+        // A lane's points i and i + C are one frame apart (C = M / BLK), so tap row q reads, for
+        // point i, the sample row q - 1 read for point i - C: the lane keeps its 16 samples in
+        // registers, moves them up by C per row and loads C new ones (always of the tile's
+        // first frame, which every tile holds).  16 + (P - 1) C sample loads and P C tap loads
+        // per lane instead of 16 P of each; the same sums in the same order.
+        constexpr int C = M / BLK;
+        float2 x[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int p = t + BLK * i;
+            x[i] = make_float2(0.f, 0.f);
+            if (p < npts) x[i] = stream_sample<U8>(a, g0 + p);
+        }
+        for (int q = 0; q < a.P; ++q) {
+            if (q) {
+#pragma unroll
+                for (int i = 15; i >= C; --i) x[i] = x[i - C];
+#pragma unroll
+                for (int i = 0; i < C; ++i) x[i] = stream_sample<U8>(a, g0 + t + BLK * i - (long)q * M);
+            }
+            float h[C];
+#pragma unroll
+            for (int j = 0; j < C; ++j) h[j] = a.taps_pm[(long)q * M + t + BLK * j];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                acc[i].x = fmaf(h[i % C], x[i].x, acc[i].x);
+                acc[i].y = fmaf(h[i % C], x[i].y, acc[i].y);
+            }
+        }
+    } else {
+        for (int q = 0; q < a.P; ++q)
+            tap_row<M, U8, BLK>(a, a.taps_pm + (long)q * M, g0 - (long)q * M, npts, acc);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) lds[fpad(t + BLK * i)] = acc[i];
+    __syncthreads();
+    tile_fft<M, false>(lds, a.tw);
+    // fpad image -> pitched image (through registers: both live in the one array)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = lds[fpad(t + BLK * i)];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int p = t + BLK * i;
+        lds[(p / M) * PITCH + p % M] = acc[i];
+    }
+    __syncthreads();
+    // transposed store: point p -> (channel p / F, frame p % F)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int p = t + BLK * i;
+        const int k = p / F, f = p % F;
+        if (f < nf) a.out[(long)k * a.ld_out + f0 + f] = lds[f * PITCH + k];
+    }
+}
+
+template <int M, bool U8>
+int launch_kind(ChanArgs a, hipStream_t s) {
+    constexpr int BLK = M >= kChanBigMinM ? 1024 : kFftBlock;
+    using Tile = ChanTile<M, BLK>;
+    constexpr size_t lds = (size_t)Tile::LDS * sizeof(float2);
+    static const bool attr = hipFuncSetAttribute((const void*)chan_tile_kernel<M, U8, BLK>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)lds) == hipSuccess;
+    if (!attr) return SDRGPU_ERR_LAUNCH;
+    a.ntiles = (unsigned)ceil_div(a.nframes, (long)Tile::F);
+    const long ncarry = std::min<long>(ceil_div(a.H, (long)BLK), 128);
+    hipLaunchKernelGGL((chan_tile_kernel<M, U8, BLK>), dim3(a.ntiles + (unsigned)ncarry), dim3(BLK),
+                       lds, s, a);
+    SDRGPU_LAUNCH_CHECK();
+    return SDRGPU_OK;
+}
+
+template <int M>
+int launch_m(int sample_kind, const ChanArgs& a, hipStream_t s) {
+    return sample_kind == SDRGPU_CU8 ? launch_kind<M, true>(a, s) : launch_kind<M, false>(a, s);
+}
+
+}  // namespace
+
+int chan_launch(int M, int sample_kind, ChanArgs a, hipStream_t s) {
+    if (!chan_size_ok((size_t)M) || a.P < 1 || a.H != (long)a.P * M - 1 || a.pend < 0 || a.pend >= M)
+        return SDRGPU_ERR_INVALID;
+    if (a.nframes != (a.pend + a.n_in) / M || a.ld_out < a.nframes) return SDRGPU_ERR_INVALID;
+    switch (M) {
+    case 2: return launch_m<2>(sample_kind, a, s);
+    case 4: return launch_m<4>(sample_kind, a, s);
+    case 8: return launch_m<8>(sample_kind, a, s);
+    case 16: return launch_m<16>(sample_kind, a, s);
+    case 32: return launch_m<32>(sample_kind, a, s);
+    case 64: return launch_m<64>(sample_kind, a, s);
+    case 128: return launch_m<128>(sample_kind, a, s);
+    case 256: return launch_m<256>(sample_kind, a, s);
+    case 512: return launch_m<512>(sample_kind, a, s);
+    case 1024: return launch_m<1024>(sample_kind, a, s);
+    case 2048: return launch_m<2048>(sample_kind, a, s);
+    default: return launch_m<4096>(sample_kind, a, s);
+    }
+}
+
+}  // namespace sdrgpu

@@ -9,7 +9,8 @@
 // Kernels (256 lanes, 16 complex points per lane = one 4096-point LDS tile per workgroup):
 //   fft_tile_kernel  -- 4096/M transforms of size M <= 4096 per workgroup: coalesced load
 //                       (frame gather folded in), up to 3 radix-{2,4,8,16} Stockham passes in
-//                       LDS (twiddles from a 4096-entry table + recurrence), collated store.
+//                       LDS (twiddles from a 4096-entry table + recurrence; fft_tile.hpp, shared
+//                       with the channelizer), collated store.
 //   four-step (M > 4096, M = M1*M2): pass A = M2-point column FFTs on 4096/M2 columns per
 //                       workgroup (rows of 4096/M2 contiguous samples -> coalesced), times
 //                       W_M^{n1 k2}, to a scratch slab; pass B = M1-point FFTs over n1 on
@@ -24,71 +25,13 @@
 #include "fft_device.hpp"
 #include "fft_frames.hpp"
 #include "fft_kernels.hpp"
+#include "fft_tile.hpp"
 
 namespace sdrgpu {
 
 using namespace fftd;
 
 namespace {
-
-constexpr int kFftBlock = 256;
-constexpr int kTile = 4096;
-__device__ __forceinline__ int fpad(int i) { return i + (i >> 4); }
-constexpr int kTileLds = kTile + kTile / 16;
-
-}  // namespace
-
-namespace {
-
-// -------- in-place Stockham pass over the 4096-point tile (all sizes compile-time) -----
-// batch of 4096/M transforms of size M; radix R; stride NS.  Each lane does 16/R butterflies.
-template <int R, int M, int NS, bool INV>
-__device__ __forceinline__ void tile_pass(float2* lds, const float2* __restrict__ tw) {
-    constexpr int NBF = 16 / R;
-    constexpr int BPT = M / R;  // butterflies per transform
-    const int t = threadIdx.x;
-    float2 v[NBF][R];
-#pragma unroll
-    for (int u = 0; u < NBF; ++u) {
-        const int g = t * NBF + u;
-        const int f = g / BPT, j = g % BPT;   // compile-time power-of-two divisors -> shifts
-        const int base = f * M;
-#pragma unroll
-        for (int r = 0; r < R; ++r) v[u][r] = lds[fpad(base + j + r * BPT)];
-        if (NS > 1) {
-            const int k = j % NS;
-            twiddle<R, INV>(v[u], tw, k * (kTile / (NS * R)));
-        }
-        Dft<R, INV>::run(v[u]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < NBF; ++u) {
-        const int g = t * NBF + u;
-        const int f = g / BPT, j = g % BPT;
-        const int k = j % NS;
-        const int o = f * M + (j / NS) * NS * R + k;
-#pragma unroll
-        for (int r = 0; r < R; ++r) lds[fpad(o + r * NS)] = v[u][r];
-    }
-    __syncthreads();
-}
-
-// radix plan: 16s first, then the remainder (M = 16^a * rem, rem in {1,2,4,8})
-template <int M, int NS, bool INV>
-__device__ __forceinline__ void tile_fft_rec(float2* lds, const float2* __restrict__ tw) {
-    if constexpr (NS < M) {
-        constexpr int LEFT = M / NS;
-        constexpr int R = LEFT >= 16 ? 16 : LEFT;
-        tile_pass<R, M, NS, INV>(lds, tw);
-        tile_fft_rec<M, NS * R, INV>(lds, tw);
-    }
-}
-
-template <int M, bool INV>
-__device__ __forceinline__ void tile_fft(float2* lds, const float2* __restrict__ tw) {
-    tile_fft_rec<M, 1, INV>(lds, tw);
-}
 
 struct TileArgs {
     FrameSrc src;
@@ -527,11 +470,7 @@ void* fft_plan_create(int M, int* status) {
     auto* p = new FftPlanDev();
     p->M = M;
     p->norm = 1.0f / sqrtf((float)M);  // f32, like fft.rs:16
-    std::vector<float2> tw(kTile);
-    for (int m = 0; m < kTile; ++m) {
-        const double ang = -2.0 * M_PI * (double)m / kTile;
-        tw[m] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-    }
+    const std::vector<float2> tw = tile_twiddles();
     bool ok = hipMalloc(&p->tw4096, kTile * sizeof(float2)) == hipSuccess &&
               hipMemcpy(p->tw4096, tw.data(), kTile * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess;
     if (ok && M > kTile) {

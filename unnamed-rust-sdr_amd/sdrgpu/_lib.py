@@ -133,6 +133,17 @@ SIGNATURES = [
     ("sdrgpu_firbank_reset", c_int, [_H]),
     ("sdrgpu_firbank_clone", c_int, [_H, _PH]),
     ("sdrgpu_firbank_destroy", None, [_H]),
+    # polyphase channelizer
+    ("sdrgpu_chan_create", c_int, [c_int, c_int, c_void_p, c_size_t, c_size_t, _PH]),
+    ("sdrgpu_chan_set_stream", c_int, [_H, c_void_p]),
+    ("sdrgpu_chan_get_stream", c_int, [_H, _PH]),
+    ("sdrgpu_chan_output_len", c_int, [_H, c_size_t, _PS]),
+    ("sdrgpu_chan_process", c_int, [_H, c_void_p, c_size_t, c_void_p, c_size_t, _PS]),
+    ("sdrgpu_chan_process_dev", c_int, [_H, c_void_p, c_size_t, c_void_p, c_size_t, _PS]),
+    ("sdrgpu_chan_sync", c_int, [_H]),
+    ("sdrgpu_chan_reset", c_int, [_H]),
+    ("sdrgpu_chan_clone", c_int, [_H, _PH]),
+    ("sdrgpu_chan_destroy", None, [_H]),
     # FFT
     ("sdrgpu_fft_plan", c_int, [c_int, c_size_t, _PH]),
     ("sdrgpu_fft_set_stream", c_int, [_H, c_void_p]),

@@ -294,6 +294,87 @@ class FirBank:
         return a.value
 
 
+# ---------------------------------------------------------------------- Channelizer
+class Channelizer:
+    """Polyphase channelizer: one wideband stream into nch channel rows.  Channel k is the
+    reference's `signal.filter(c_k).decimate(rate / nch)` with the complex taps
+    c_k[n] = taps[n] * exp(+2j*pi*k*(n+1)/nch) (fir.rs:23-32, adapters/mod.rs:30-37): the band
+    centred at +k*rate/nch, low-passed by the real prototype `taps`, every nch-th sample kept.
+    nch: a power of two, 2..4096.  sample_kind C64 or CU8 (rtl_tcp bytes); outputs are C64,
+    channel-major, the layout FirBank and Pll read."""
+
+    def __init__(self, taps, nch: int, sample_kind: int = C64, device: int = 0, _handle=None):
+        taps = np.asarray(taps)
+        if np.iscomplexobj(taps) or taps.ndim != 1:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Channelizer: taps must be a real 1-D array")
+        self.taps = _as_c(taps, F32)
+        self.nch = nch
+        self.sample_kind = sample_kind
+        self.device = device
+        self._h = ctypes.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            check(lib().sdrgpu_chan_create(device, sample_kind, self.taps.ctypes.data,
+                                           self.taps.size, nch, ctypes.byref(self._h)),
+                  "sdrgpu_chan_create")
+
+    def close(self):
+        if self._h:
+            lib().sdrgpu_chan_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clone(self) -> "Channelizer":
+        h = ctypes.c_void_p()
+        check(lib().sdrgpu_chan_clone(self._h, ctypes.byref(h)), "sdrgpu_chan_clone")
+        return Channelizer(self.taps, self.nch, self.sample_kind, self.device, _handle=h)
+
+    def reset(self):
+        check(lib().sdrgpu_chan_reset(self._h), "sdrgpu_chan_reset")
+
+    def set_stream(self, stream_ptr: Optional[int]):
+        check(lib().sdrgpu_chan_set_stream(self._h, stream_ptr), "sdrgpu_chan_set_stream")
+
+    def stream(self) -> int:
+        s = ctypes.c_void_p()
+        check(lib().sdrgpu_chan_get_stream(self._h, ctypes.byref(s)), "sdrgpu_chan_get_stream")
+        return s.value or 0
+
+    def output_len(self, n_in: int) -> int:
+        """Outputs per channel the next process() call produces for n_in inputs."""
+        n = ctypes.c_size_t()
+        check(lib().sdrgpu_chan_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
+        return n.value
+
+    def process(self, x) -> np.ndarray:
+        """x: (n,) host samples (CU8: 2n bytes or (n, 2)) -> (nch, n_out) complex64."""
+        x = _as_c(x, self.sample_kind)
+        n_in = _nsamp(x.reshape(-1), self.sample_kind)
+        n_out = self.output_len(n_in)
+        out = np.empty((self.nch, max(n_out, 1)), dtype=np.complex64)
+        got = ctypes.c_size_t()
+        check(lib().sdrgpu_chan_process(self._h, x.ctypes.data, n_in, out.ctypes.data,
+                                        out.shape[1], ctypes.byref(got)), "sdrgpu_chan_process")
+        return out[:, :got.value]
+
+    def process_dev(self, d_in_ptr: int, n_in: int, d_out_ptr: int, ld_out: int) -> int:
+        """Enqueue on the handle's stream with device pointers; channel k's outputs go to
+        d_out + k*ld_out samples.  Returns n_out (per channel)."""
+        got = ctypes.c_size_t()
+        check(lib().sdrgpu_chan_process_dev(self._h, d_in_ptr, n_in, d_out_ptr, ld_out,
+                                            ctypes.byref(got)), "sdrgpu_chan_process_dev")
+        return got.value
+
+    def sync(self):
+        check(lib().sdrgpu_chan_sync(self._h), "sdrgpu_chan_sync")
+
+
 # --------------------------------------------------------------------------- Biquad
 @dataclass(frozen=True)
 class BiquadD:
