@@ -55,6 +55,8 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true", help="timing-only ablation builds: skip the c3 / c5 spot checks")
     ap.add_argument("--chan-log2n", type=int, default=26)
+    ap.add_argument("--chan-oversample", type=int, default=1, choices=[1, 2, 4],
+                    help="chan only: frames 1024/os apart, 1024 x os*2^16 outputs")
     ap.add_argument("--no-fir-route", action="store_true",
                     help="chan only: skip timing the one-Fir-per-channel route")
     ap.add_argument("--gpus", type=int, default=1,
@@ -612,12 +614,20 @@ def bench_fm(args):
 
 
 # ------------------------------------------------------------------------------ chan
-def chan_ref_f64(h, M, seg):
+def chan_ref_f64(h, M, seg, os=1, m0=0):
     """The channelizer's polyphase form in f64: seg holds (P-1)*M samples of
-    history, then whole frames; returns (M, frames)."""
+    history, then whole frames; returns (M, frames).  os > 1: the frames are D = M/os apart, seg
+    starts at the window of frame m0 (P*M samples) and holds D more per further frame, and the
+    result carries rot(k, m) = exp(-2j pi k (m+1) / os) as its exact values."""
     P = -(-h.size // M)
     hp = np.zeros(P * M)
     hp[:h.size] = h
+    if os > 1:
+        D = M // os
+        win = np.lib.stride_tricks.sliding_window_view(np.asarray(seg, np.complex128), P * M)[::D]
+        v = (win * hp[::-1]).reshape(-1, P, M).sum(axis=1)
+        e = (np.arange(M)[:, None] * (m0 + 1 + np.arange(v.shape[0]))[None, :]) % os
+        return np.fft.fft(v, axis=1).T * np.array([1, -1j, -1, 1j])[e * (4 // os)]
     fr = np.asarray(seg, np.complex128).reshape(-1, M)
     nf = fr.shape[0] - (P - 1)
     v = sum(hp[q * M + M - 1 - np.arange(M)] * fr[P - 1 - q:P - 1 - q + nf] for q in range(P))
@@ -632,6 +642,8 @@ def bench_chan(args):
     and at the end, all 1024 channels, against the f64 polyphase form (the oracle's own f32 sum
     over 8192 complex taps is 1.08e-5 of RMS from f64, outside the tolerance it would check).
     The handle streams, so the history entering a step is the end of the step before it.
+    --chan-oversample 2 or 4: the same stream into 1024 x os*65536 outputs (frames 1024/os
+    apart, 8 B in + 8*os B out per input sample), checked against the f64 form with rot.
     fir_route: the only route without the channelizer -- one sdrgpu_fir per channel with c64
     taps h[n] exp(2j pi k (n+1) / M) and decimation M over the same input -- timed for 8 handles
     on one stream and scaled to 1024."""
@@ -639,8 +651,11 @@ def bench_chan(args):
     import sdrgpu
     from sdrgpu.device import DeviceBuffer, synchronize
     M, n = 1024, 1 << args.chan_log2n
-    L, n_out = 8 * M, n // M
+    osf = args.chan_oversample
+    D = M // osf
+    L, n_out = 8 * M, n // D
     P = L // M
+    assert n_out % osf == 0  # every step starts at a frame count that is a multiple of os
     h = ss.firwin(L, 1.0 / M).astype(np.float32)
     pat_n = min(n, 1 << 22)
     first_call = args.steps + args.warmup == 1
@@ -648,22 +663,24 @@ def bench_chan(args):
     res = {"config": f"chan: polyphase channelizer, {M} channels, firwin({L}, 1/{M}) prototype, "
                      f"2^{args.chan_log2n} samples -> {M} x {n_out} c64",
            "metric": "complex Msamples/s (input)"}
+    if osf > 1:
+        res.update({"oversample": osf, "algorithmic_bytes": 8 + 8 * osf})
 
     def check(pat):
         worst = 0.0
         for m0 in (0, n_out // 2 + 3, n_out - 8):
-            g = np.arange((m0 + 1 - P) * M, (m0 + 8) * M)
+            g = np.arange((m0 + 1) * D - P * M, (m0 + 8) * D)
             seg = pat[g % pat_n]
             if first_call:
                 seg = np.where(g >= 0, seg, 0)
-            ref = chan_ref_f64(h, M, seg)
+            ref = chan_ref_f64(h, M, seg, osf, m0)
             got = np.stack([y.download(8, offset_bytes=8 * (k * n_out + m0)) for k in range(M)])
             worst = max(worst, float(np.abs(got - ref).max() / np.sqrt(np.mean(np.abs(ref) ** 2))))
         assert worst <= 1e-5 or args.no_check, worst
         return worst
 
     # c64 leg
-    ch = sdrgpu.Channelizer(h, M)
+    ch = sdrgpu.Channelizer(h, M, oversample=osf) if osf > 1 else sdrgpu.Channelizer(h, M)
     x = DeviceBuffer.empty(n)
     fill(x, n, 31)
 
@@ -671,10 +688,10 @@ def bench_chan(args):
         assert ch.process_dev(x.ptr, n, y.ptr, n_out) == n_out
 
     wall, ms = time_events(step, ch.stream(), args.steps, args.warmup, lambda: (ch.sync(), synchronize()))
-    res.update({"value": round(n / (ms * 1e-3) / 1e6, 1), "roofline": roof(16, n, ms),
+    res.update({"value": round(n / (ms * 1e-3) / 1e6, 1), "roofline": roof(8 + 8 * osf, n, ms),
                 "wall_ms_per_step": round(wall * 1e3, 3),
                 "spot_check_max_over_rms": check(cplx_pattern(pat_n, 31))})
-    if not args.no_fir_route:
+    if not args.no_fir_route and osf == 1:
         nh = 8
         k_taps = [(h.astype(np.float64) * np.exp(2j * np.pi * k * (np.arange(L) + 1.0) / M)).astype(np.complex64)
                   for k in range(nh)]
@@ -699,7 +716,8 @@ def bench_chan(args):
         del firs, outs
     del x
     # rtl_tcp u8 leg
-    ch8 = sdrgpu.Channelizer(h, M, sample_kind=sdrgpu.CU8)
+    ch8 = (sdrgpu.Channelizer(h, M, sample_kind=sdrgpu.CU8, oversample=osf) if osf > 1
+           else sdrgpu.Channelizer(h, M, sample_kind=sdrgpu.CU8))
     pat8 = np.random.default_rng(32).integers(0, 256, size=2 * pat_n, dtype=np.uint8)
     x8 = DeviceBuffer.empty(2 * n, np.uint8)
     for off in range(0, 2 * n, pat8.size):
@@ -710,9 +728,11 @@ def bench_chan(args):
 
     wall8, ms8 = time_events(step8, ch8.stream(), args.steps, args.warmup, lambda: (ch8.sync(), synchronize()))
     p8 = (pat8.astype(np.float64) - 128.0) / 128.0
-    res["cu8"] = {"value": round(n / (ms8 * 1e-3) / 1e6, 1), "roofline": roof(10, n, ms8),
+    res["cu8"] = {"value": round(n / (ms8 * 1e-3) / 1e6, 1), "roofline": roof(2 + 8 * osf, n, ms8),
                   "wall_ms_per_step": round(wall8 * 1e3, 3),
                   "spot_check_max_over_rms": check(p8[0::2] + 1j * p8[1::2])}
+    if osf > 1:
+        res["cu8"]["algorithmic_bytes"] = 2 + 8 * osf
     return res
 
 

@@ -229,11 +229,31 @@ void sdrgpu_firbank_destroy(sdrgpu_firbank* h);
  * zero-padded to a multiple of M and every channel of a frame sums all its branches, so an
  * inf / NaN sample makes every channel of every frame whose ceil(ntaps/M)*M-sample window
  * holds it non-finite (the chains: only the outputs whose ntaps-sample window holds it);
- * frames whose window does not hold it are unaffected. */
+ * frames whose window does not hold it are unaffected.
+ *
+ * Oversampled bank (sdrgpu_chan_create_os): oversample = os in {1, 2, 4}, os <= nch, makes the
+ * frames D = M/os samples apart, so every channel row leaves at os times the channel spacing.
+ * Frame m counts from the stream start across all calls and exists once (m+1)*D samples have
+ * been seen:
+ *   y_k[m] = rot(k, m) * sum_{n<ntaps} taps[n] * exp(+j*2*pi*k*(n+1)/M) * x[m*D + D-1 - n]
+ *   rot(k, m) = exp(-j*2*pi*k*(m+1)*D/M) = exp(-j*2*pi*k*(m+1)/os),               x[<0] = 0.
+ * The sum is the chain signal.filter(c_k).decimate(rate / D) with the same c_k (Decimate keeps
+ * stream indices D-1, 2D-1, ...); rot puts channel k at baseband -- without it the band-pass
+ * chain leaves channel k centred at k/os cycles per output sample.  rot is a power of -1
+ * (os = 2) or of -j (os = 4), a swap / negation of components, exact in f32; with os = 1 it is
+ * 1 and the definition is the one above.  n_out = floor((seen + n_in)/D) - floor(seen/D); the
+ * state, the partition invariance and the non-finite statement (for a frame's
+ * ceil(ntaps/M)*M-sample window) hold as above.  oversample 0 is SDRGPU_ERR_INVALID; a value
+ * other than 1, 2, 4 or above nch is SDRGPU_ERR_UNSUPPORTED.  sdrgpu_chan_create is
+ * sdrgpu_chan_create_os with oversample 1.  sdrgpu_chan_get_decim returns D.  A clone keeps
+ * the oversampling, the sample count and the history. */
 typedef struct sdrgpu_chan sdrgpu_chan;
 
 int sdrgpu_chan_create(int device, int sample_kind, const float* taps, size_t ntaps, size_t nch,
                        sdrgpu_chan** out);
+int sdrgpu_chan_create_os(int device, int sample_kind, const float* taps, size_t ntaps, size_t nch,
+                          uint32_t oversample, sdrgpu_chan** out);
+int sdrgpu_chan_get_decim(const sdrgpu_chan* h, size_t* decim);
 int sdrgpu_chan_set_stream(sdrgpu_chan* h, void* hip_stream);
 int sdrgpu_chan_get_stream(const sdrgpu_chan* h, void** hip_stream);
 int sdrgpu_chan_output_len(const sdrgpu_chan* h, size_t n_in, size_t* n_out);

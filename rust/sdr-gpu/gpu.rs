@@ -289,6 +289,77 @@ impl<A> Drop for GpuFirBank<A> {
     }
 }
 
+// -------------------------------------------------------------------- channelizer
+
+/// One wideband `Complex<f32>` stream into `nch` channel rows (include/sdrgpu.h
+/// `sdrgpu_chan`): channel k replaces `signal.filter(c_k).decimate(rate / decim)` with
+/// `c_k[n] = taps[n] * exp(j 2 pi k (n+1) / nch)` (fir.rs:23-32, adapters/mod.rs:30-37).
+/// `new` is critically sampled (`decim = nch`); `with_oversample` puts the frames
+/// `decim = nch / oversample` apart (oversample 2 or 4) and centres every channel at
+/// baseband: output m of channel k since the stream start carries
+/// `exp(-j 2 pi k (m+1) / oversample)`, a power of -1 or -j.
+pub struct Channelizer {
+    h: *mut sys::sdrgpu_chan,
+    nch: usize,
+}
+
+unsafe impl Send for Channelizer {}
+
+impl Channelizer {
+    pub fn new(taps: &[f32], nch: usize) -> Result<Self> {
+        Self::with_oversample(taps, nch, 1)
+    }
+
+    pub fn with_oversample(taps: &[f32], nch: usize, oversample: u32) -> Result<Self> {
+        let mut h = ptr::null_mut();
+        check(unsafe {
+            sys::sdrgpu_chan_create_os(DEVICE, sys::SDRGPU_C64, taps.as_ptr(), taps.len(), nch,
+                                       oversample, &mut h)
+        })?;
+        Ok(Channelizer { h, nch })
+    }
+
+    /// Input samples per output frame, `nch / oversample`.
+    pub fn decim(&self) -> usize {
+        let mut d = 0;
+        check(unsafe { sys::sdrgpu_chan_get_decim(self.h, &mut d) }).expect("sdrgpu_chan_get_decim");
+        d
+    }
+
+    /// One block of any length; `output` gets `nch` rows of the returned number of samples
+    /// (leading dimension = that number), the layout `GpuFirBank` and the PLL batch read.
+    pub fn process(&mut self, input: &[Complex<f32>], output: &mut Vec<Complex<f32>>) -> Result<usize> {
+        let mut m = 0;
+        check(unsafe { sys::sdrgpu_chan_output_len(self.h, input.len(), &mut m) })?;
+        output.resize(self.nch * m.max(1), Complex::new(0.0, 0.0));
+        check(unsafe {
+            sys::sdrgpu_chan_process(self.h, input.as_ptr() as *const _, input.len(),
+                                     output.as_mut_ptr() as *mut _, m.max(1), &mut m)
+        })?;
+        output.truncate(self.nch * m);
+        Ok(m)
+    }
+
+    pub fn reset(&mut self) -> Result<()> {
+        check(unsafe { sys::sdrgpu_chan_reset(self.h) })
+    }
+}
+
+impl Clone for Channelizer {
+    // the copy carries the oversampling, the sample count and the history
+    fn clone(&self) -> Self {
+        let mut h = ptr::null_mut();
+        check(unsafe { sys::sdrgpu_chan_clone(self.h, &mut h) }).expect("sdrgpu_chan_clone");
+        Channelizer { h, nch: self.nch }
+    }
+}
+
+impl Drop for Channelizer {
+    fn drop(&mut self) {
+        unsafe { sys::sdrgpu_chan_destroy(self.h) }
+    }
+}
+
 // ------------------------------------------------------------------ biquad designs
 
 /// The filter designs the PLL and the biquad stage take: `BiquadD` (src/filter/biquad.rs:

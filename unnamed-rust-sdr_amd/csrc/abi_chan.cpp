@@ -1,8 +1,10 @@
 // abi_chan.cpp -- C ABI of the polyphase channelizer (sdrgpu_chan, include/sdrgpu.h).
 //
 // Replaces M chains signal.filter(c_k).decimate(rate / M) (Fir with Complex taps, reference
-// src/filter/fir.rs:23-32; Decimate, src/signal/adapters/mod.rs:30-37) by one handle.  Stream
-// state -- the last P*M - 1 samples, of which seen % M are not framed yet, and the sample count
+// src/filter/fir.rs:23-32; Decimate, src/signal/adapters/mod.rs:30-37) by one handle; an
+// oversampled bank (os = 2 or 4) replaces filter(c_k).decimate(rate / D), D = M / os, times the
+// baseband rotation rot(k, m) = exp(-2 pi i k (m + 1) / os).  Stream
+// state -- the last P*M - 1 samples, of which seen % D are not framed yet, and the sample count
 // -- is carried on the device across calls, so block partitioning never changes the outputs
 // (chan.hip computes every frame with the same arithmetic wherever it falls).
 #include <new>
@@ -23,6 +25,7 @@ struct sdrgpu_chan {
     int device = 0;
     int sk = SDRGPU_C64;
     int M = 2, P = 1;
+    int os = 1;                            // oversampling factor; frames are D = M / os apart
     std::vector<float> taps;               // as given (clone)
     float* d_taps_pm = nullptr;            // P*M, polyphase-major (chan_kernels.hpp)
     float2* d_tw = nullptr;
@@ -34,7 +37,8 @@ struct sdrgpu_chan {
 
     size_t in_bytes() const { return kind_bytes(sk); }
     size_t H() const { return (size_t)P * M - 1; }
-    size_t out_len(size_t n_in) const { return (size_t)((seen % (unsigned)M + n_in) / (unsigned)M); }
+    unsigned D() const { return (unsigned)(M / os); }
+    size_t out_len(size_t n_in) const { return (size_t)((seen % D() + n_in) / D()); }
 
     void free_all() {
         DeviceGuard g(device);
@@ -61,16 +65,18 @@ struct sdrgpu_chan {
         return SDRGPU_OK;
     }
 
-    int init(int dev, int sample_kind, const float* h, size_t ntaps, size_t nch) {
-        if (!h || ntaps == 0 || nch == 0) return SDRGPU_ERR_INVALID;
+    int init(int dev, int sample_kind, const float* h, size_t ntaps, size_t nch, uint32_t oversample) {
+        if (!h || ntaps == 0 || nch == 0 || oversample == 0) return SDRGPU_ERR_INVALID;
         if (sample_kind != SDRGPU_C64 && sample_kind != SDRGPU_CU8)
             return sample_kind == SDRGPU_F32 ? SDRGPU_ERR_UNSUPPORTED : SDRGPU_ERR_INVALID;
         if (!chan_size_ok(nch) || (ntaps + nch - 1) / nch > kChanMaxP) return SDRGPU_ERR_UNSUPPORTED;
+        if (!chan_os_ok(nch, oversample)) return SDRGPU_ERR_UNSUPPORTED;
         int st = check_device(dev);
         if (st) return st;
         device = dev;
         sk = sample_kind;
         M = (int)nch;
+        os = (int)oversample;
         P = (int)((ntaps + nch - 1) / nch);
         taps.assign(h, h + ntaps);
 
@@ -104,7 +110,9 @@ struct sdrgpu_chan {
         a.hist = d_hist[cur];
         a.hist_next = d_hist[cur ^ 1];
         a.H = (long)H();
-        a.pend = (long)(seen % (unsigned)M);
+        a.pend = (long)(seen % D());
+        a.os = os;
+        a.rot0 = (int)((seen / D() + 1) % (unsigned)os);
         a.nframes = (long)n_out;
         a.P = P;
         a.taps_pm = d_taps_pm;
@@ -137,7 +145,7 @@ struct sdrgpu_chan {
     }
 
     int clone_into(sdrgpu_chan* dst) const {
-        int st = dst->init(device, sk, taps.data(), taps.size(), (size_t)M);
+        int st = dst->init(device, sk, taps.data(), taps.size(), (size_t)M, (uint32_t)os);
         if (st) return st;
         DeviceGuard g(device);
         dst->seen = seen;
@@ -170,9 +178,22 @@ int make_handle(sdrgpu_chan** out, Init init) {
 
 extern "C" {
 
+int sdrgpu_chan_create_os(int device, int sample_kind, const float* taps, size_t ntaps, size_t nch,
+                          uint32_t oversample, sdrgpu_chan** out) {
+    return make_handle(out, [&](sdrgpu_chan* h) {
+        return h->init(device, sample_kind, taps, ntaps, nch, oversample);
+    });
+}
+
 int sdrgpu_chan_create(int device, int sample_kind, const float* taps, size_t ntaps, size_t nch,
                        sdrgpu_chan** out) {
-    return make_handle(out, [&](sdrgpu_chan* h) { return h->init(device, sample_kind, taps, ntaps, nch); });
+    return sdrgpu_chan_create_os(device, sample_kind, taps, ntaps, nch, 1, out);
+}
+
+int sdrgpu_chan_get_decim(const sdrgpu_chan* h, size_t* decim) {
+    if (!h || !decim) return SDRGPU_ERR_INVALID;
+    *decim = h->D();
+    return SDRGPU_OK;
 }
 
 int sdrgpu_chan_clone(const sdrgpu_chan* h, sdrgpu_chan** out) {

@@ -23,6 +23,15 @@
 // 16384 points (136 KiB of LDS, one workgroup per CU), which makes a channel's run of frames
 // 128 B at M = 1024 instead of 32 B and reads (F + P - 1)/F = 1.44 instead of 2.75 times the
 // input at P = 8 (measured: DESIGN.md 3.4a).
+//
+// Oversampled bank (template parameter OS = 1, 2, 4; OS <= M): the frames are D = M / OS samples
+// apart.  With the window start w = (m+1) D - P M the same two lines hold,
+//   v_r[m] = sum_{q<P} h[q M + M-1 - r] x[(m+1) D - (q+1) M + r],   chain_k[m] = DFT_M(v[m])_k,
+// and chain_k[m] is signal.filter(c_k).decimate(rate / D): r counts from the window, so no
+// phase term appears.  Only the tile's addressing changes -- point p = f M + r of row q is
+// stream sample g0 + f D + r - q M, still contiguous in runs of M -- and the store multiplies by
+// rot(k, m) = exp(-2 pi i k (m+1) / OS), a power of -1 or -i, which centres channel k at
+// baseband; m counts from the stream start (ChanArgs::rot0).  OS = 1 is the code above.
 #include <algorithm>
 
 #include "chan_kernels.hpp"
@@ -62,9 +71,16 @@ __device__ __forceinline__ float2 stream_sample(const ChanArgs& a, long g) {
     return g < 0 ? a.hist[a.H + g] : block_sample<U8>(a.in, g);
 }
 
-// tap row q of the tile: acc[i] += h[q M + r] x[b + p], p = t + BLK i, r = p % M; points at or
-// past npts (frames the block does not hold) take x = 0.
-template <int M, bool U8, int BLK>
+// stream offset of tile point p = f M + r from the tile's first one: frames are D = M / OS apart
+template <int M, int OS>
+__device__ __forceinline__ int tile_off(int p) {
+    if constexpr (OS == 1) return p;
+    else return (p / M) * (M / OS) + p % M;
+}
+
+// tap row q of the tile: acc[i] += h[q M + r] x[b + f D + r], p = t + BLK i = f M + r; points at
+// or past npts (frames the block does not hold) take x = 0.
+template <int M, int OS, bool U8, int BLK>
 __device__ __forceinline__ void tap_row(const ChanArgs& a, const float* __restrict__ hq, long b,
                                         int npts, float2 (&acc)[16]) {
     const int t = threadIdx.x;
@@ -75,7 +91,7 @@ __device__ __forceinline__ void tap_row(const ChanArgs& a, const float* __restri
         const int p = t + BLK * i;
         h[i] = hq[p % M];
         x[i] = make_float2(0.f, 0.f);
-        if (p < npts) x[i] = stream_sample<U8>(a, b + p);
+        if (p < npts) x[i] = stream_sample<U8>(a, b + tile_off<M, OS>(p));
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -84,9 +100,17 @@ __device__ __forceinline__ void tap_row(const ChanArgs& a, const float* __restri
     }
 }
 
-template <int M, bool U8, int BLK>
+// (-j)^e v, e = 0..3: rot(k, m) of an oversampled bank, exact
+__device__ __forceinline__ float2 rot_quarter(float2 v, int e) {
+    if (e & 1) v = make_float2(v.y, -v.x);
+    if (e & 2) v = make_float2(-v.x, -v.y);
+    return v;
+}
+
+template <int M, int OS, bool U8, int BLK>
 __global__ __launch_bounds__(BLK) void chan_tile_kernel(ChanArgs a) {
     constexpr int F = ChanTile<M, BLK>::F, PITCH = ChanTile<M, BLK>::PITCH;
+    constexpr int D = M / OS;  // frame stride
     extern __shared__ float2 lds[];  // ChanTile::LDS
     const int t = threadIdx.x;
     if (blockIdx.x >= a.ntiles) {
@@ -99,30 +123,32 @@ __global__ __launch_bounds__(BLK) void chan_tile_kernel(ChanArgs a) {
     const long f0 = (long)blockIdx.x * F;
     const int nf = (int)min((long)F, a.nframes - f0);
     const int npts = nf * M;
-    const long g0 = f0 * M - a.pend;  // stream sample of tile point 0 in tap row 0
+    const long g0 = (f0 + 1) * D - M - a.pend;  // stream sample of tile point 0 in tap row 0
     float2 acc[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = make_float2(0.f, 0.f);
-    if constexpr (M >= BLK) {
-        // A lane's points i and i + C are one frame apart (C = M / BLK), so tap row q reads, for
-        // point i, the sample row q - 1 read for point i - C: the lane keeps its 16 samples in
-        // registers, moves them up by C per row and loads C new ones (always of the tile's
-        // first frame, which every tile holds).  16 + (P - 1) C sample loads and P C tap loads
-        // per lane instead of 16 P of each; the same sums in the same order.
-        constexpr int C = M / BLK;
+    if constexpr (M >= BLK && OS * (M / BLK) < 16) {
+        // A lane's points i and i + C are one frame apart (C = M / BLK) and frame f - OS lies one M
+        // back, so tap row q reads, for point i, the sample row q - 1 read for point i - OS C: the
+        // lane keeps its 16 samples in registers, moves them up by S = OS C per row and loads S
+        // new ones (always of the tile's first OS frames at q >= 1, which lie in front of the
+        // first frame's newest M samples, so every tile holds them).  16 + (P - 1) S sample loads
+        // and P C tap loads per lane instead of 16 P of each; the same sums in the same order.
+        constexpr int C = M / BLK, S = OS * C;
         float2 x[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int p = t + BLK * i;
             x[i] = make_float2(0.f, 0.f);
-            if (p < npts) x[i] = stream_sample<U8>(a, g0 + p);
+            if (p < npts) x[i] = stream_sample<U8>(a, g0 + tile_off<M, OS>(p));
         }
         for (int q = 0; q < a.P; ++q) {
             if (q) {
 #pragma unroll
-                for (int i = 15; i >= C; --i) x[i] = x[i - C];
+                for (int i = 15; i >= S; --i) x[i] = x[i - S];
 #pragma unroll
-                for (int i = 0; i < C; ++i) x[i] = stream_sample<U8>(a, g0 + t + BLK * i - (long)q * M);
+                for (int i = 0; i < S; ++i)
+                    x[i] = stream_sample<U8>(a, g0 + tile_off<M, OS>(t + BLK * i) - (long)q * M);
             }
             float h[C];
 #pragma unroll
@@ -133,9 +159,34 @@ __global__ __launch_bounds__(BLK) void chan_tile_kernel(ChanArgs a) {
                 acc[i].y = fmaf(h[i % C], x[i].y, acc[i].y);
             }
         }
+    } else if constexpr (M >= BLK) {
+        // OS C = 16 (M = 4096, OS = 4): a row shares nothing with the row before it.  Within a
+        // row, point (f + 1, r) is point (f, r + D), the same lane's point i + C / OS, so the 16
+        // points of a lane are U = (F - 1) C / OS + C distinct samples, BLK apart: U P sample
+        // loads (7 P) and P C tap loads per lane.  Samples past the block belong only to frames
+        // the block does not hold, which are not stored.
+        constexpr int C = M / BLK, U = (F - 1) * C / OS + C;
+        static_assert(C % OS == 0, "frames of a lane overlap in whole points");
+        for (int q = 0; q < a.P; ++q) {
+            float2 x[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const long g = g0 + t + BLK * u - (long)q * M;
+                x[u] = make_float2(0.f, 0.f);
+                if (g < a.n_in) x[u] = stream_sample<U8>(a, g);
+            }
+            float h[C];
+#pragma unroll
+            for (int j = 0; j < C; ++j) h[j] = a.taps_pm[(long)q * M + t + BLK * j];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                acc[i].x = fmaf(h[i % C], x[i / C * (C / OS) + i % C].x, acc[i].x);
+                acc[i].y = fmaf(h[i % C], x[i / C * (C / OS) + i % C].y, acc[i].y);
+            }
+        }
     } else {
         for (int q = 0; q < a.P; ++q)
-            tap_row<M, U8, BLK>(a, a.taps_pm + (long)q * M, g0 - (long)q * M, npts, acc);
+            tap_row<M, OS, U8, BLK>(a, a.taps_pm + (long)q * M, g0 - (long)q * M, npts, acc);
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) lds[fpad(t + BLK * i)] = acc[i];
@@ -156,38 +207,57 @@ __global__ __launch_bounds__(BLK) void chan_tile_kernel(ChanArgs a) {
     for (int i = 0; i < 16; ++i) {
         const int p = t + BLK * i;
         const int k = p / F, f = p % F;
-        if (f < nf) a.out[(long)k * a.ld_out + f0 + f] = lds[f * PITCH + k];
+        if constexpr (OS == 1) {
+            if (f < nf) a.out[(long)k * a.ld_out + f0 + f] = lds[f * PITCH + k];
+        } else {
+            // baseband centring: rot(k, m) = (-j)^(4/OS k (m + 1)), m + 1 = a.rot0 + f0 + f mod OS
+            const int e = (k * (int)((a.rot0 + f0 + f) & (OS - 1)) & (OS - 1)) * (4 / OS);
+            if (f < nf) a.out[(long)k * a.ld_out + f0 + f] = rot_quarter(lds[f * PITCH + k], e);
+        }
     }
 }
 
-template <int M, bool U8>
+template <int M, int OS, bool U8>
 int launch_kind(ChanArgs a, hipStream_t s) {
     constexpr int BLK = M >= kChanBigMinM ? 1024 : kFftBlock;
     using Tile = ChanTile<M, BLK>;
     constexpr size_t lds = (size_t)Tile::LDS * sizeof(float2);
-    static const bool attr = hipFuncSetAttribute((const void*)chan_tile_kernel<M, U8, BLK>,
+    static const bool attr = hipFuncSetAttribute((const void*)chan_tile_kernel<M, OS, U8, BLK>,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)lds) == hipSuccess;
     if (!attr) return SDRGPU_ERR_LAUNCH;
     a.ntiles = (unsigned)ceil_div(a.nframes, (long)Tile::F);
     const long ncarry = std::min<long>(ceil_div(a.H, (long)BLK), 128);
-    hipLaunchKernelGGL((chan_tile_kernel<M, U8, BLK>), dim3(a.ntiles + (unsigned)ncarry), dim3(BLK),
+    hipLaunchKernelGGL((chan_tile_kernel<M, OS, U8, BLK>), dim3(a.ntiles + (unsigned)ncarry), dim3(BLK),
                        lds, s, a);
     SDRGPU_LAUNCH_CHECK();
     return SDRGPU_OK;
 }
 
+template <int M, int OS>
+int launch_os(int sample_kind, const ChanArgs& a, hipStream_t s) {
+    if constexpr (OS > M) return SDRGPU_ERR_INVALID;
+    else return sample_kind == SDRGPU_CU8 ? launch_kind<M, OS, true>(a, s) : launch_kind<M, OS, false>(a, s);
+}
+
 template <int M>
 int launch_m(int sample_kind, const ChanArgs& a, hipStream_t s) {
-    return sample_kind == SDRGPU_CU8 ? launch_kind<M, true>(a, s) : launch_kind<M, false>(a, s);
+    switch (a.os) {
+    case 1: return launch_os<M, 1>(sample_kind, a, s);
+    case 2: return launch_os<M, 2>(sample_kind, a, s);
+    default: return launch_os<M, 4>(sample_kind, a, s);
+    }
 }
 
 }  // namespace
 
 int chan_launch(int M, int sample_kind, ChanArgs a, hipStream_t s) {
-    if (!chan_size_ok((size_t)M) || a.P < 1 || a.H != (long)a.P * M - 1 || a.pend < 0 || a.pend >= M)
+    if (!chan_size_ok((size_t)M) || !chan_os_ok((size_t)M, (unsigned)a.os) || a.P < 1 ||
+        a.H != (long)a.P * M - 1)
         return SDRGPU_ERR_INVALID;
-    if (a.nframes != (a.pend + a.n_in) / M || a.ld_out < a.nframes) return SDRGPU_ERR_INVALID;
+    const long D = M / a.os;
+    if (a.pend < 0 || a.pend >= D || a.rot0 < 0 || a.rot0 >= a.os) return SDRGPU_ERR_INVALID;
+    if (a.nframes != (a.pend + a.n_in) / D || a.ld_out < a.nframes) return SDRGPU_ERR_INVALID;
     switch (M) {
     case 2: return launch_m<2>(sample_kind, a, s);
     case 4: return launch_m<4>(sample_kind, a, s);

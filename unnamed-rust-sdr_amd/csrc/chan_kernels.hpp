@@ -8,10 +8,13 @@ namespace sdrgpu {
 // Channel counts chan_launch has a kernel for: the LDS tile sizes, powers of two 2..4096.
 inline bool chan_size_ok(size_t M) { return M >= 2 && M <= 4096 && (M & (M - 1)) == 0; }
 
+// Oversampling factors of a bank of M channels: frames are D = M / os samples apart.
+inline bool chan_os_ok(size_t M, unsigned os) { return (os == 1 || os == 2 || os == 4) && os <= M; }
+
 // One block of a stream.  The handle keeps the last H = P*M - 1 stream samples (zero before the
-// stream start); `pend` = seen % M of them are not framed yet.  With the block appended, sample
+// stream start); `pend` = seen % D of them are not framed yet.  With the block appended, sample
 // g >= 0 is in[g] and sample g < 0 is hist[H + g]; frame j of the block (j < nframes) covers
-// samples [(j + 1 - P)*M - pend, (j + 1)*M - pend).
+// samples [(j + 1)*D - P*M - pend, (j + 1)*D - pend).
 struct ChanArgs {
     const void* in;        // c64 or rtl_tcp u8 pairs
     long n_in;
@@ -25,6 +28,8 @@ struct ChanArgs {
     const float2* tw;      // W_4096 (fft_tile.hpp: tile_twiddles)
     float2* out;           // out[k*ld_out + j]
     long ld_out;
+    int os;                // oversampling factor: 1, 2 or 4, at most M
+    int rot0;              // (frames before this block + 1) % os: the phase of rot(k, m)
     unsigned ntiles;       // workgroups that compute frames; the ones after them carry the history
 };
 

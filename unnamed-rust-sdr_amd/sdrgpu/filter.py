@@ -301,9 +301,14 @@ class Channelizer:
     c_k[n] = taps[n] * exp(+2j*pi*k*(n+1)/nch) (fir.rs:23-32, adapters/mod.rs:30-37): the band
     centred at +k*rate/nch, low-passed by the real prototype `taps`, every nch-th sample kept.
     nch: a power of two, 2..4096.  sample_kind C64 or CU8 (rtl_tcp bytes); outputs are C64,
-    channel-major, the layout FirBank and Pll read."""
+    channel-major, the layout FirBank and Pll read.
+    oversample = 2 or 4 (at most nch) puts the frames decim = nch / oversample samples apart:
+    channel k is `signal.filter(c_k).decimate(rate / decim)` times exp(-2j*pi*k*(m+1)/oversample)
+    for its m-th output since the stream start, which centres every channel at baseband at
+    oversample times the channel spacing."""
 
-    def __init__(self, taps, nch: int, sample_kind: int = C64, device: int = 0, _handle=None):
+    def __init__(self, taps, nch: int, sample_kind: int = C64, device: int = 0,
+                 oversample: int = 1, _handle=None):
         taps = np.asarray(taps)
         if np.iscomplexobj(taps) or taps.ndim != 1:
             raise _lib.SdrGpuError(_lib.ERR_INVALID, "Channelizer: taps must be a real 1-D array")
@@ -311,13 +316,17 @@ class Channelizer:
         self.nch = nch
         self.sample_kind = sample_kind
         self.device = device
+        self.oversample = oversample
         self._h = ctypes.c_void_p()
         if _handle is not None:
             self._h = _handle
         else:
-            check(lib().sdrgpu_chan_create(device, sample_kind, self.taps.ctypes.data,
-                                           self.taps.size, nch, ctypes.byref(self._h)),
-                  "sdrgpu_chan_create")
+            if not 0 <= oversample < 1 << 32:
+                raise _lib.SdrGpuError(_lib.ERR_INVALID, "Channelizer: oversample out of range")
+            check(lib().sdrgpu_chan_create_os(device, sample_kind, self.taps.ctypes.data,
+                                              self.taps.size, nch, oversample,
+                                              ctypes.byref(self._h)),
+                  "sdrgpu_chan_create_os")
 
     def close(self):
         if self._h:
@@ -333,7 +342,8 @@ class Channelizer:
     def clone(self) -> "Channelizer":
         h = ctypes.c_void_p()
         check(lib().sdrgpu_chan_clone(self._h, ctypes.byref(h)), "sdrgpu_chan_clone")
-        return Channelizer(self.taps, self.nch, self.sample_kind, self.device, _handle=h)
+        return Channelizer(self.taps, self.nch, self.sample_kind, self.device, self.oversample,
+                           _handle=h)
 
     def reset(self):
         check(lib().sdrgpu_chan_reset(self._h), "sdrgpu_chan_reset")
@@ -345,6 +355,13 @@ class Channelizer:
         s = ctypes.c_void_p()
         check(lib().sdrgpu_chan_get_stream(self._h, ctypes.byref(s)), "sdrgpu_chan_get_stream")
         return s.value or 0
+
+    @property
+    def decim(self) -> int:
+        """Input samples per output frame, nch / oversample."""
+        d = ctypes.c_size_t()
+        check(lib().sdrgpu_chan_get_decim(self._h, ctypes.byref(d)), "sdrgpu_chan_get_decim")
+        return d.value
 
     def output_len(self, n_in: int) -> int:
         """Outputs per channel the next process() call produces for n_in inputs."""
