@@ -57,6 +57,10 @@ def parse():
     ap.add_argument("--chan-log2n", type=int, default=26)
     ap.add_argument("--chan-oversample", type=int, default=1, choices=[1, 2, 4],
                     help="chan only: frames 1024/os apart, 1024 x os*2^16 outputs")
+    ap.add_argument("--chan-nch", type=int, default=1024,
+                    help="chan only: channel count N (2..4096, prime factors <= 13), prototype "
+                         "firwin(8*N, 1/N); not a power of two: the largest multiple of N samples "
+                         "in 2^log2n")
     ap.add_argument("--no-fir-route", action="store_true",
                     help="chan only: skip timing the one-Fir-per-channel route")
     ap.add_argument("--gpus", type=int, default=1,
@@ -646,12 +650,17 @@ def bench_chan(args):
     apart, 8 B in + 8*os B out per input sample), checked against the f64 form with rot.
     fir_route: the only route without the channelizer -- one sdrgpu_fir per channel with c64
     taps h[n] exp(2j pi k (n+1) / M) and decimation M over the same input -- timed for 8 handles
-    on one stream and scaled to 1024."""
+    on one stream and scaled to 1024.
+    --chan-nch N: N channels instead of 1024 with the prototype firwin(8 N, 1/N); an N that is
+    not a power of two (the general-M kernel) takes the largest multiple of N
+    samples in 2^log2n, so that every step holds whole frames."""
     import scipy.signal as ss
     import sdrgpu
     from sdrgpu.device import DeviceBuffer, synchronize
-    M, n = 1024, 1 << args.chan_log2n
+    M, n = args.chan_nch, 1 << args.chan_log2n
     osf = args.chan_oversample
+    assert M % osf == 0, "--chan-oversample must divide --chan-nch"
+    n -= n % M  # 2^log2n for a power of two
     D = M // osf
     L, n_out = 8 * M, n // D
     P = L // M
@@ -661,7 +670,7 @@ def bench_chan(args):
     first_call = args.steps + args.warmup == 1
     y = DeviceBuffer.empty(M * n_out)
     res = {"config": f"chan: polyphase channelizer, {M} channels, firwin({L}, 1/{M}) prototype, "
-                     f"2^{args.chan_log2n} samples -> {M} x {n_out} c64",
+                     f"{f'2^{args.chan_log2n}' if n == 1 << args.chan_log2n else n} samples -> {M} x {n_out} c64",
            "metric": "complex Msamples/s (input)"}
     if osf > 1:
         res.update({"oversample": osf, "algorithmic_bytes": 8 + 8 * osf})
@@ -670,7 +679,7 @@ def bench_chan(args):
         worst = 0.0
         for m0 in (0, n_out // 2 + 3, n_out - 8):
             g = np.arange((m0 + 1) * D - P * M, (m0 + 8) * D)
-            seg = pat[g % pat_n]
+            seg = pat[np.where(g >= 0, g, g + n) % pat_n]  # g < 0: the end of the step before
             if first_call:
                 seg = np.where(g >= 0, seg, 0)
             ref = chan_ref_f64(h, M, seg, osf, m0)
@@ -692,7 +701,7 @@ def bench_chan(args):
                 "wall_ms_per_step": round(wall * 1e3, 3),
                 "spot_check_max_over_rms": check(cplx_pattern(pat_n, 31))})
     if not args.no_fir_route and osf == 1:
-        nh = 8
+        nh = min(8, M)
         k_taps = [(h.astype(np.float64) * np.exp(2j * np.pi * k * (np.arange(L) + 1.0) / M)).astype(np.complex64)
                   for k in range(nh)]
         firs = [sdrgpu.filter.Fir(t, decim=M, sample_kind=sdrgpu.C64).design() for t in k_taps]
@@ -721,7 +730,7 @@ def bench_chan(args):
     pat8 = np.random.default_rng(32).integers(0, 256, size=2 * pat_n, dtype=np.uint8)
     x8 = DeviceBuffer.empty(2 * n, np.uint8)
     for off in range(0, 2 * n, pat8.size):
-        x8.upload(pat8, offset_bytes=off)
+        x8.upload(pat8[:min(pat8.size, 2 * n - off)], offset_bytes=off)
 
     def step8():
         assert ch8.process_dev(x8.ptr, n, y.ptr, n_out) == n_out

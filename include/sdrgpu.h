@@ -246,13 +246,28 @@ void sdrgpu_firbank_destroy(sdrgpu_firbank* h);
  * ceil(ntaps/M)*M-sample window) hold as above.  oversample 0 is SDRGPU_ERR_INVALID; a value
  * other than 1, 2, 4 or above nch is SDRGPU_ERR_UNSUPPORTED.  sdrgpu_chan_create is
  * sdrgpu_chan_create_os with oversample 1.  sdrgpu_chan_get_decim returns D.  A clone keeps
- * the oversampling, the sample count and the history. */
+ * the oversampling, the sample count and the history.
+ *
+ * Any smooth channel count (sdrgpu_chan_create_any): nch = M is 2..4096 with every prime factor
+ * <= 13 (9 FM channels of 200 kHz in 1.8 MS/s, 12 in 2.4 MS/s, 96, 100, 1000, ...), oversample
+ * is in {1, 2, 4} and divides nch (D = M/os a whole number of samples, so rot stays the exact
+ * power of -1 or -j above), ceil(ntaps / nch) <= 64.  y_k[m], n_out, the channel-major output
+ * with ld_out, the carried state, the bit-identical partitions, overlapping d_out and the
+ * non-finite statement are those above with M = nch, and every other sdrgpu_chan_* function
+ * takes the handle.  Null or zero arguments and oversample 0 are SDRGPU_ERR_INVALID; a prime
+ * factor above 13, nch 1 or above 4096, an oversample that does not divide nch or is not 1, 2
+ * or 4, too many taps per branch and SDRGPU_F32 are SDRGPU_ERR_UNSUPPORTED, all before the
+ * device is looked at.  For a power-of-two nch the call is sdrgpu_chan_create_os (same kernels,
+ * bit-identical outputs).  sdrgpu_chan_create and sdrgpu_chan_create_os keep their contract:
+ * they take power-of-two nch only, any other nch is SDRGPU_ERR_UNSUPPORTED. */
 typedef struct sdrgpu_chan sdrgpu_chan;
 
 int sdrgpu_chan_create(int device, int sample_kind, const float* taps, size_t ntaps, size_t nch,
                        sdrgpu_chan** out);
 int sdrgpu_chan_create_os(int device, int sample_kind, const float* taps, size_t ntaps, size_t nch,
                           uint32_t oversample, sdrgpu_chan** out);
+int sdrgpu_chan_create_any(int device, int sample_kind, const float* taps, size_t ntaps, size_t nch,
+                           uint32_t oversample, sdrgpu_chan** out);
 int sdrgpu_chan_get_decim(const sdrgpu_chan* h, size_t* decim);
 int sdrgpu_chan_set_stream(sdrgpu_chan* h, void* hip_stream);
 int sdrgpu_chan_get_stream(const sdrgpu_chan* h, void** hip_stream);

@@ -310,11 +310,19 @@ impl Channelizer {
         Self::with_oversample(taps, nch, 1)
     }
 
+    /// `nch`: 2..4096 with every prime factor <= 13; `oversample` 1, 2 or 4, a divisor of `nch`.
+    /// A power-of-two `nch` goes through `sdrgpu_chan_create_os`, any other count (9 FM channels
+    /// in 1.8 MS/s, 12 in 2.4 MS/s) through `sdrgpu_chan_create_any`.
     pub fn with_oversample(taps: &[f32], nch: usize, oversample: u32) -> Result<Self> {
         let mut h = ptr::null_mut();
         check(unsafe {
-            sys::sdrgpu_chan_create_os(DEVICE, sys::SDRGPU_C64, taps.as_ptr(), taps.len(), nch,
-                                       oversample, &mut h)
+            if nch.is_power_of_two() {
+                sys::sdrgpu_chan_create_os(DEVICE, sys::SDRGPU_C64, taps.as_ptr(), taps.len(), nch,
+                                           oversample, &mut h)
+            } else {
+                sys::sdrgpu_chan_create_any(DEVICE, sys::SDRGPU_C64, taps.as_ptr(), taps.len(), nch,
+                                            oversample, &mut h)
+            }
         })?;
         Ok(Channelizer { h, nch })
     }

@@ -6,7 +6,9 @@
 // baseband rotation rot(k, m) = exp(-2 pi i k (m + 1) / os).  Stream
 // state -- the last P*M - 1 samples, of which seen % D are not framed yet, and the sample count
 // -- is carried on the device across calls, so block partitioning never changes the outputs
-// (chan.hip computes every frame with the same arithmetic wherever it falls).
+// (chan.hip computes every frame with the same arithmetic wherever it falls).  A channel count
+// that is not a power of two (sdrgpu_chan_create_any) runs chan_gen.hip's kernel with the tile
+// plan and the W_M table made here at create; everything else of the handle is the same.
 #include <new>
 #include <vector>
 
@@ -26,6 +28,8 @@ struct sdrgpu_chan {
     int sk = SDRGPU_C64;
     int M = 2, P = 1;
     int os = 1;                            // oversampling factor; frames are D = M / os apart
+    bool general = false;                  // M is not a power of two: chan_gen.hip, `gen`, d_tw = W_M
+    ChanGenPlan gen;
     std::vector<float> taps;               // as given (clone)
     float* d_taps_pm = nullptr;            // P*M, polyphase-major (chan_kernels.hpp)
     float2* d_tw = nullptr;
@@ -65,11 +69,15 @@ struct sdrgpu_chan {
         return SDRGPU_OK;
     }
 
-    int init(int dev, int sample_kind, const float* h, size_t ntaps, size_t nch, uint32_t oversample) {
+    // any_m: take every channel count chan_gen_plan has a tile for, not only the powers of two
+    int init(int dev, int sample_kind, const float* h, size_t ntaps, size_t nch, uint32_t oversample,
+             bool any_m) {
         if (!h || ntaps == 0 || nch == 0 || oversample == 0) return SDRGPU_ERR_INVALID;
         if (sample_kind != SDRGPU_C64 && sample_kind != SDRGPU_CU8)
             return sample_kind == SDRGPU_F32 ? SDRGPU_ERR_UNSUPPORTED : SDRGPU_ERR_INVALID;
-        if (!chan_size_ok(nch) || (ntaps + nch - 1) / nch > kChanMaxP) return SDRGPU_ERR_UNSUPPORTED;
+        general = !chan_size_ok(nch);
+        if (general && !(any_m && chan_gen_plan(nch, gen))) return SDRGPU_ERR_UNSUPPORTED;
+        if ((ntaps + nch - 1) / nch > kChanMaxP) return SDRGPU_ERR_UNSUPPORTED;
         if (!chan_os_ok(nch, oversample)) return SDRGPU_ERR_UNSUPPORTED;
         int st = check_device(dev);
         if (st) return st;
@@ -86,7 +94,7 @@ struct sdrgpu_chan {
         // taps_pm[q*M + r] = h[q*M + M-1-r]: lane r of a wave reads consecutive floats
         std::vector<float> pm((size_t)P * M, 0.0f);
         for (size_t n = 0; n < ntaps; ++n) pm[n / M * M + (M - 1 - n % M)] = h[n];
-        const std::vector<float2> tw = fftd::tile_twiddles();
+        const std::vector<float2> tw = general ? twiddles(M) : fftd::tile_twiddles();
         SDRGPU_HIP_TRY(hipMalloc(&d_taps_pm, pm.size() * sizeof(float)));
         SDRGPU_HIP_TRY(hipMemcpy(d_taps_pm, pm.data(), pm.size() * sizeof(float), hipMemcpyHostToDevice));
         SDRGPU_HIP_TRY(hipMalloc(&d_tw, tw.size() * sizeof(float2)));
@@ -119,7 +127,8 @@ struct sdrgpu_chan {
         a.tw = d_tw;
         a.out = static_cast<float2*>(d_out);
         a.ld_out = (long)ld_out;
-        if ((st = chan_launch(M, sk, a, stream.cur))) return st;
+        if ((st = general ? chan_gen_launch(gen, sk, a, stream.cur) : chan_launch(M, sk, a, stream.cur)))
+            return st;
         cur ^= 1;
         seen += n_in;
         return SDRGPU_OK;
@@ -145,7 +154,7 @@ struct sdrgpu_chan {
     }
 
     int clone_into(sdrgpu_chan* dst) const {
-        int st = dst->init(device, sk, taps.data(), taps.size(), (size_t)M, (uint32_t)os);
+        int st = dst->init(device, sk, taps.data(), taps.size(), (size_t)M, (uint32_t)os, general);
         if (st) return st;
         DeviceGuard g(device);
         dst->seen = seen;
@@ -181,7 +190,14 @@ extern "C" {
 int sdrgpu_chan_create_os(int device, int sample_kind, const float* taps, size_t ntaps, size_t nch,
                           uint32_t oversample, sdrgpu_chan** out) {
     return make_handle(out, [&](sdrgpu_chan* h) {
-        return h->init(device, sample_kind, taps, ntaps, nch, oversample);
+        return h->init(device, sample_kind, taps, ntaps, nch, oversample, false);
+    });
+}
+
+int sdrgpu_chan_create_any(int device, int sample_kind, const float* taps, size_t ntaps, size_t nch,
+                           uint32_t oversample, sdrgpu_chan** out) {
+    return make_handle(out, [&](sdrgpu_chan* h) {
+        return h->init(device, sample_kind, taps, ntaps, nch, oversample, true);
     });
 }
 

@@ -1,4 +1,5 @@
-// chan.hip -- polyphase channelizer for gfx950: one wideband stream into M channel rows.
+// chan.hip -- polyphase channelizer for gfx950: one wideband stream into M channel rows, M a
+// power of two (any other M whose prime factors are at most 13: chan_gen.hip).
 //
 // Semantics: channel k is signal.filter(c_k).decimate(rate / M) with the complex taps
 // c_k[n] = h[n] exp(+2 pi i k (n+1) / M) (Fir with Complex taps, reference src/filter/fir.rs:23-32;
@@ -34,8 +35,7 @@
 // baseband; m counts from the stream start (ChanArgs::rot0).  OS = 1 is the code above.
 #include <algorithm>
 
-#include "chan_kernels.hpp"
-#include "fft_frames.hpp"
+#include "chan_device.hpp"
 #include "fft_tile.hpp"
 
 namespace sdrgpu {
@@ -58,18 +58,6 @@ struct ChanTile {
     static constexpr int PITCH = M + (F >= 32 ? 1 : 32 / F);
     static constexpr int LDS = F * PITCH > T + T / 16 ? F * PITCH : T + T / 16;  // float2
 };
-
-template <bool U8>
-__device__ __forceinline__ float2 block_sample(const void* in, long g) {
-    if constexpr (U8) return u8_sample(static_cast<const unsigned short*>(in)[g]);
-    else return static_cast<const float2*>(in)[g];
-}
-
-// sample g of the history followed by the block
-template <bool U8>
-__device__ __forceinline__ float2 stream_sample(const ChanArgs& a, long g) {
-    return g < 0 ? a.hist[a.H + g] : block_sample<U8>(a.in, g);
-}
 
 // stream offset of tile point p = f M + r from the tile's first one: frames are D = M / OS apart
 template <int M, int OS>
@@ -98,13 +86,6 @@ __device__ __forceinline__ void tap_row(const ChanArgs& a, const float* __restri
         acc[i].x = fmaf(h[i], x[i].x, acc[i].x);
         acc[i].y = fmaf(h[i], x[i].y, acc[i].y);
     }
-}
-
-// (-j)^e v, e = 0..3: rot(k, m) of an oversampled bank, exact
-__device__ __forceinline__ float2 rot_quarter(float2 v, int e) {
-    if (e & 1) v = make_float2(v.y, -v.x);
-    if (e & 2) v = make_float2(-v.x, -v.y);
-    return v;
 }
 
 template <int M, int OS, bool U8, int BLK>
@@ -252,12 +233,7 @@ int launch_m(int sample_kind, const ChanArgs& a, hipStream_t s) {
 }  // namespace
 
 int chan_launch(int M, int sample_kind, ChanArgs a, hipStream_t s) {
-    if (!chan_size_ok((size_t)M) || !chan_os_ok((size_t)M, (unsigned)a.os) || a.P < 1 ||
-        a.H != (long)a.P * M - 1)
-        return SDRGPU_ERR_INVALID;
-    const long D = M / a.os;
-    if (a.pend < 0 || a.pend >= D || a.rot0 < 0 || a.rot0 >= a.os) return SDRGPU_ERR_INVALID;
-    if (a.nframes != (a.pend + a.n_in) / D || a.ld_out < a.nframes) return SDRGPU_ERR_INVALID;
+    if (!chan_size_ok((size_t)M) || !chan_block_ok(M, a)) return SDRGPU_ERR_INVALID;
     switch (M) {
     case 2: return launch_m<2>(sample_kind, a, s);
     case 4: return launch_m<4>(sample_kind, a, s);

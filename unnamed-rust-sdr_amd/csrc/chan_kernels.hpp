@@ -1,15 +1,18 @@
-// chan_kernels.hpp -- internal launch interface of the polyphase channelizer (chan.hip).
+// chan_kernels.hpp -- internal launch interface of the polyphase channelizer (chan.hip:
+// power-of-two channel counts; chan_gen.hip: any count whose prime factors are at most 13).
 #pragma once
 
 #include "common.hpp"
+#include "fft_gen_tile.hpp"
 
 namespace sdrgpu {
 
 // Channel counts chan_launch has a kernel for: the LDS tile sizes, powers of two 2..4096.
 inline bool chan_size_ok(size_t M) { return M >= 2 && M <= 4096 && (M & (M - 1)) == 0; }
 
-// Oversampling factors of a bank of M channels: frames are D = M / os samples apart.
-inline bool chan_os_ok(size_t M, unsigned os) { return (os == 1 || os == 2 || os == 4) && os <= M; }
+// Oversampling factors of a bank of M channels: frames are D = M / os samples apart, a whole
+// number (for a power-of-two M: os <= M).
+inline bool chan_os_ok(size_t M, unsigned os) { return (os == 1 || os == 2 || os == 4) && M % os == 0; }
 
 // One block of a stream.  The handle keeps the last H = P*M - 1 stream samples (zero before the
 // stream start); `pend` = seen % D of them are not framed yet.  With the block appended, sample
@@ -25,15 +28,38 @@ struct ChanArgs {
     long nframes;
     int P;                 // taps per polyphase branch
     const float* taps_pm;  // P*M: taps_pm[q*M + r] = h[q*M + M-1-r], zero past the last tap
-    const float2* tw;      // W_4096 (fft_tile.hpp: tile_twiddles)
+    const float2* tw;      // chan_launch: W_4096 (fft_tile.hpp: tile_twiddles); chan_gen_launch: W_M
     float2* out;           // out[k*ld_out + j]
     long ld_out;
-    int os;                // oversampling factor: 1, 2 or 4, at most M
+    int os;                // oversampling factor: 1, 2 or 4, a divisor of M
     int rot0;              // (frames before this block + 1) % os: the phase of rot(k, m)
     unsigned ntiles;       // workgroups that compute frames; the ones after them carry the history
 };
 
+// what both launchers require of a block of a bank of M channels
+inline bool chan_block_ok(int M, const ChanArgs& a) {
+    if (!chan_os_ok((size_t)M, (unsigned)a.os) || a.P < 1 || a.H != (long)a.P * M - 1) return false;
+    const long D = M / a.os;
+    if (a.pend < 0 || a.pend >= D || a.rot0 < 0 || a.rot0 >= a.os) return false;
+    return a.nframes == (a.pend + a.n_in) / D && a.ld_out >= a.nframes;
+}
+
 // sample_kind SDRGPU_C64 or SDRGPU_CU8; one launch: frames, then the history carry
 int chan_launch(int M, int sample_kind, ChanArgs a, hipStream_t s);
+
+// General M (chan_gen.hip): the tile of a bank of M channels, made once per handle.  A workgroup
+// owns F = floor(tile / M) whole frames x M channels; tile points at or past F*M are idle.
+struct ChanGenPlan {
+    int M = 0;
+    int tile = 0;        // points per LDS tile: 4096 (256 lanes) or 16384 (1024 lanes)
+    int F = 0;           // frames per tile
+    int pitch = 0;       // of the [frame][channel] image the transposed store reads
+    fftd::FastDiv df;    // F
+    fftd::RadixList rl;  // radices(M); rl.dn divides by M
+};
+// false unless M is 2..4096 with every prime factor <= 13
+bool chan_gen_plan(size_t M, ChanGenPlan& plan);
+// a.tw: W_M (twiddles(M)) on the device
+int chan_gen_launch(const ChanGenPlan& plan, int sample_kind, ChanArgs a, hipStream_t s);
 
 }  // namespace sdrgpu

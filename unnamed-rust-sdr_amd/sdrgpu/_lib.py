@@ -137,6 +137,8 @@ SIGNATURES = [
     ("sdrgpu_chan_create", c_int, [c_int, c_int, c_void_p, c_size_t, c_size_t, _PH]),
     ("sdrgpu_chan_create_os", c_int,
      [c_int, c_int, c_void_p, c_size_t, c_size_t, c_uint32, _PH]),
+    ("sdrgpu_chan_create_any", c_int,
+     [c_int, c_int, c_void_p, c_size_t, c_size_t, c_uint32, _PH]),
     ("sdrgpu_chan_get_decim", c_int, [_H, _PS]),
     ("sdrgpu_chan_set_stream", c_int, [_H, c_void_p]),
     ("sdrgpu_chan_get_stream", c_int, [_H, _PH]),

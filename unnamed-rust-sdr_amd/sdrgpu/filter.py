@@ -300,9 +300,10 @@ class Channelizer:
     reference's `signal.filter(c_k).decimate(rate / nch)` with the complex taps
     c_k[n] = taps[n] * exp(+2j*pi*k*(n+1)/nch) (fir.rs:23-32, adapters/mod.rs:30-37): the band
     centred at +k*rate/nch, low-passed by the real prototype `taps`, every nch-th sample kept.
-    nch: a power of two, 2..4096.  sample_kind C64 or CU8 (rtl_tcp bytes); outputs are C64,
-    channel-major, the layout FirBank and Pll read.
-    oversample = 2 or 4 (at most nch) puts the frames decim = nch / oversample samples apart:
+    nch: 2..4096 with every prime factor <= 13 (9, 12, 96, 100, 1000, ...; a power of two goes
+    through sdrgpu_chan_create_os, any other count through sdrgpu_chan_create_any).  sample_kind
+    C64 or CU8 (rtl_tcp bytes); outputs are C64, channel-major, the layout FirBank and Pll read.
+    oversample = 2 or 4 (a divisor of nch) puts the frames decim = nch / oversample samples apart:
     channel k is `signal.filter(c_k).decimate(rate / decim)` times exp(-2j*pi*k*(m+1)/oversample)
     for its m-th output since the stream start, which centres every channel at baseband at
     oversample times the channel spacing."""
@@ -323,10 +324,10 @@ class Channelizer:
         else:
             if not 0 <= oversample < 1 << 32:
                 raise _lib.SdrGpuError(_lib.ERR_INVALID, "Channelizer: oversample out of range")
-            check(lib().sdrgpu_chan_create_os(device, sample_kind, self.taps.ctypes.data,
-                                              self.taps.size, nch, oversample,
-                                              ctypes.byref(self._h)),
-                  "sdrgpu_chan_create_os")
+            pow2 = nch >= 1 and nch & (nch - 1) == 0
+            name = "sdrgpu_chan_create_os" if pow2 else "sdrgpu_chan_create_any"
+            check(getattr(lib(), name)(device, sample_kind, self.taps.ctypes.data, self.taps.size,
+                                       nch, oversample, ctypes.byref(self._h)), name)
 
     def close(self):
         if self._h:
