@@ -17,6 +17,8 @@ per config:
       (v-128)/128 fused into the FIR load, 2^28 samples
   chan  polyphase channelizer, 1024 channels, 8192 taps,    8 B in + 8 B out / sample (u8 leg:
       2^26 c64 samples (not part of `all`)                  2 B in + 8 B out), HBM roof
+  synth polyphase synthesis bank, 1024 rows x 2^16*os      8*os B in + 8 B out / output sample,
+      frames -> 2^26 c64 samples (not part of `all`)        HBM roof
 
 Multi-GPU (c5): `python -m torch.distributed.run --nproc-per-node N bench_configs.py
 --config c5`; each rank filters its resident channel shard (weak: 8192/N channels per rank
@@ -42,7 +44,7 @@ HBM_GBS = 8000.0
 
 def parse():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="all", choices=["c1", "c3", "c4", "c5", "c2u8", "c2host", "c2pinned", "src", "ex", "fm", "chan", "all"])
+    ap.add_argument("--config", default="all", choices=["c1", "c3", "c4", "c5", "c2u8", "c2host", "c2pinned", "src", "ex", "fm", "chan", "synth", "all"])
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--c3-log2n", type=int, default=28)
@@ -56,7 +58,7 @@ def parse():
     ap.add_argument("--no-check", action="store_true", help="timing-only ablation builds: skip the c3 / c5 spot checks")
     ap.add_argument("--chan-log2n", type=int, default=26)
     ap.add_argument("--chan-oversample", type=int, default=1, choices=[1, 2, 4],
-                    help="chan only: frames 1024/os apart, 1024 x os*2^16 outputs")
+                    help="chan and synth: frames 1024/os apart, 1024 x os*2^16 frames")
     ap.add_argument("--chan-nch", type=int, default=1024,
                     help="chan only: channel count N (2..4096, prime factors <= 13), prototype "
                          "firwin(8*N, 1/N); not a power of two: the largest multiple of N samples "
@@ -745,6 +747,71 @@ def bench_chan(args):
     return res
 
 
+# ----------------------------------------------------------------------------- synth
+def synth_ref_f64(g, M, os, seg, m0):
+    """The synthesis bank's polyphase form in f64: seg is (M, Q - 1 + F), frames
+    m0 - (Q - 1) .. m0 + F - 1 of every row (Q = P os); returns the F D samples from m0 D on."""
+    D, L = M // os, g.size
+    P = -(-L // M)
+    Q = P * os
+    gp = np.zeros(P * M)
+    gp[:L] = g
+    m = m0 - (Q - 1) + np.arange(seg.shape[1])
+    e = (np.arange(M)[:, None] * (m + 1)[None, :]) % os
+    w = np.fft.ifft(np.asarray(seg, np.complex128) * np.array([1, 1j, -1, -1j])[e * (4 // os)], axis=0) * M
+    r = (np.arange(P * M) - L) % M
+    out = np.zeros((seg.shape[1] + Q) * D, np.complex128)
+    for i in range(seg.shape[1]):
+        out[i * D:i * D + P * M] += gp * w[r, i]
+    return out[(Q - 1) * D:seg.shape[1] * D]
+
+
+def bench_synth(args):
+    """Polyphase synthesis bank (sdrgpu.Synthesizer): 1024 channel rows of 2^16*os frames into
+    one stream of 2^26 samples, prototype firwin(8192, 1/1024) (8*os B in + 8 B out per output
+    sample); rows resident, event-timed on the handle's stream.  Spot check of the timed output
+    (the last step's): 8 frames' worth of samples at the start, in the middle and at the end
+    against the f64 polyphase form.  The handle streams, so the frames in front of a step are
+    the end of the step before it.  --chan-nch N: N rows with firwin(8 N, 1/N);
+    --chan-oversample and --chan-log2n (output samples) as for chan."""
+    import scipy.signal as ss
+    import sdrgpu
+    from sdrgpu.device import DeviceBuffer, synchronize
+    M, n, osf = args.chan_nch, 1 << args.chan_log2n, args.chan_oversample
+    assert M & (M - 1) == 0 and osf <= M, "--chan-nch: a power of two, at least --chan-oversample"
+    D = M // osf
+    L, frames = 8 * M, n // D
+    Q = L // M * osf
+    assert frames % osf == 0 and frames >= Q + 8
+    g = ss.firwin(L, 1.0 / M).astype(np.float32)
+    pat_n = min(M * frames, 1 << 22)
+    first_call = args.steps + args.warmup == 1
+    rows, y = DeviceBuffer.empty(M * frames), DeviceBuffer.empty(n)
+    fill(rows, M * frames, 33)
+    pat = cplx_pattern(pat_n, 33)
+    sy = sdrgpu.Synthesizer(g, M, oversample=osf)
+
+    def step():
+        assert sy.process_dev(rows.ptr, frames, frames, y.ptr, n) == n
+
+    wall, ms = time_events(step, sy.stream(), args.steps, args.warmup, lambda: (sy.sync(), synchronize()))
+    worst = 0.0
+    for m0 in (0, frames // 2 + 3, frames - 8):
+        j = m0 - (Q - 1) + np.arange(Q - 1 + 8)
+        seg = pat[(np.arange(M)[:, None] * frames + np.where(j >= 0, j, j + frames)[None, :]) % pat_n]
+        if first_call:
+            seg = np.where(j[None, :] >= 0, seg, 0)
+        ref = synth_ref_f64(g, M, osf, seg, m0)
+        got = y.download(8 * D, offset_bytes=8 * m0 * D)
+        worst = max(worst, float(np.abs(got - ref).max() / np.sqrt(np.mean(np.abs(ref) ** 2))))
+    assert worst <= 1e-5 or args.no_check, worst
+    return {"config": f"synth: polyphase synthesis bank, {M} rows x {frames} frames, firwin({L}, 1/{M}) "
+                      f"prototype -> 2^{args.chan_log2n} c64 samples",
+            "metric": "complex Msamples/s (output)", "oversample": osf, "algorithmic_bytes": 8 * osf + 8,
+            "value": round(n / (ms * 1e-3) / 1e6, 1), "roofline": roof(8 * osf + 8, n, ms),
+            "wall_ms_per_step": round(wall * 1e3, 3), "spot_check_max_over_rms": worst}
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -756,7 +823,7 @@ def main():
     for c in todo:
         r = {"c1": bench_c1, "c3": bench_c3, "c4": bench_c4, "c5": bench_c5, "c2u8": bench_c2u8,
              "c2host": bench_c2host, "c2pinned": bench_c2pinned, "src": bench_src, "ex": bench_ex,
-             "fm": bench_fm, "chan": bench_chan}[c](args)
+             "fm": bench_fm, "chan": bench_chan, "synth": bench_synth}[c](args)
         for line in (r if isinstance(r, list) else [r]):
             if line is not None:
                 print(json.dumps(line), flush=True)

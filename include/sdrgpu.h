@@ -163,7 +163,8 @@ int sdrgpu_fir_process(sdrgpu_fir* h, const void* in, size_t n_in, void* out,
  * shifted): the handle then filters a device copy of the input, so the results are those of an
  * out-of-place call (the kernels store output tiles while other workgroups still read the
  * input under them).  The same holds for sdrgpu_firbank_process_dev, sdrgpu_chan_process_dev,
- * sdrgpu_fft_exec_dev, sdrgpu_rfft_exec_dev and sdrgpu_stft_process_dev. */
+ * sdrgpu_synth_process_dev, sdrgpu_fft_exec_dev, sdrgpu_rfft_exec_dev and
+ * sdrgpu_stft_process_dev. */
 int sdrgpu_fir_process_dev(sdrgpu_fir* h, const void* d_in, size_t n_in, void* d_out,
                            size_t out_cap, size_t* n_out);
 /* HOST pointers, asynchronous (the Block adapter's producer/consumer split,
@@ -280,6 +281,59 @@ int sdrgpu_chan_sync(sdrgpu_chan* h);
 int sdrgpu_chan_reset(sdrgpu_chan* h);
 int sdrgpu_chan_clone(const sdrgpu_chan* h, sdrgpu_chan** out);
 void sdrgpu_chan_destroy(sdrgpu_chan* h);
+
+/* Polyphase synthesis bank: nch = M channel rows back into one wideband stream, the way back
+ * from sdrgpu_chan.  No reference counterpart (the crate has no interpolator); the definition
+ * is fixed here.  Rows s_k[m] are C64, frame m counts from the stream start across all calls,
+ * oversample = os, D = M/os output samples per frame, g = taps is a real prototype of L = ntaps
+ * taps, rot(k, m) = exp(-j*2*pi*k*(m+1)/os) is the factor the analysis bank applies:
+ *   f_k[n] = g[n] * exp(-j*2*pi*k*(L - n)/M)                          n = 0..L-1
+ *   x^[t]  = sum_k sum_m conj(rot(k, m)) * s_k[m] * f_k[t - m*D]      0 <= t - m*D < L
+ *          = sum_k exp(+j*2*pi*k*(t + D - L)/M) * sum_m g[t - m*D] * s_k[m].
+ * Each row is un-rotated (exact: a power of -1 or -j), zero-stuffed by D with sample m at
+ * stream index m*D, filtered with f_k -- for a symmetric g the time-reversed conjugate of the
+ * analysis filter c_k -- and the M results are summed, unscaled.  x^[t] depends only on frames
+ * m <= floor(t/D): a call with n_frames frames per channel emits exactly the n_frames*D samples
+ * t = m0*D .. (m0 + n_frames)*D - 1 (m0 frames seen before), with no latency and no pending
+ * remainder.  Computed in the polyphase form, P = ceil(L/M), g zero-padded to P*M (DESIGN.md
+ * 3.4b):
+ *   s'_k[m] = conj(rot(k, m)) * s_k[m]
+ *   w_m[r]  = sum_k s'_k[m] * exp(+j*2*pi*k*r/M)            (unscaled inverse M-point DFT)
+ *   x^[t]   = sum_{m: 0 <= t - m*D < P*M} g[n] * w_m[(n - L) mod M],   n = t - m*D,
+ * within the parity tolerance of the double sum.  Round trip: sdrgpu_chan with a prototype that
+ * passes the synthesis band (h = firwin(L, 1.5/M), g = firwin(L, 1/M), os >= 2) gives back the
+ * input delayed by L - D samples with gain 1/D.
+ * Input layout: channel k's m-th frame of the call is at in + k*ld_in + m (C64, ld_in in
+ * samples) -- what sdrgpu_chan_process_dev writes with ld_out = ld_in; gaps between rows are
+ * never read.  Output: one dense C64 stream.  nch: a power of two, 2..4096; oversample in
+ * {1, 2, 4}, <= nch; ceil(ntaps / D) <= 64; anything else is SDRGPU_ERR_UNSUPPORTED.  Null or
+ * zero arguments and oversample 0 are SDRGPU_ERR_INVALID; both classes are rejected before the
+ * device is looked at.  ld_in < n_frames is SDRGPU_ERR_INVALID; out_cap < n_frames*D is
+ * SDRGPU_ERR_OUTPUT_CAP with nothing written; n_frames 0 is OK with *n_out = 0.
+ * State (the last P*os - 1 frames of every channel, the frame count) is kept on the device and
+ * carries across calls: any partition of the frame stream into calls -- 1-frame calls, 0-frame
+ * calls and calls shorter than P*os included -- gives bit-identical output.  reset returns to
+ * the zero state; a clone keeps taps, oversampling, frame count and history and gets its own
+ * stream.  d_out may overlap the input rows (see sdrgpu_fir_process_dev).
+ * Non-finite samples: the padded taps are summed like the others, so an inf / NaN s_k[m] makes
+ * every output t in [m*D, m*D + P*M) non-finite; all other outputs are bit-identical to a
+ * clean run. */
+typedef struct sdrgpu_synth sdrgpu_synth;
+
+int sdrgpu_synth_create(int device, const float* taps, size_t ntaps, size_t nch,
+                        uint32_t oversample, sdrgpu_synth** out);
+int sdrgpu_synth_get_interp(const sdrgpu_synth* h, size_t* interp);   /* D */
+int sdrgpu_synth_set_stream(sdrgpu_synth* h, void* hip_stream);
+int sdrgpu_synth_get_stream(const sdrgpu_synth* h, void** hip_stream);
+int sdrgpu_synth_output_len(const sdrgpu_synth* h, size_t n_frames, size_t* n_out);  /* n_frames*D */
+int sdrgpu_synth_process(sdrgpu_synth* h, const void* in, size_t ld_in, size_t n_frames, void* out,
+                         size_t out_cap, size_t* n_out);
+int sdrgpu_synth_process_dev(sdrgpu_synth* h, const void* d_in, size_t ld_in, size_t n_frames,
+                             void* d_out, size_t out_cap, size_t* n_out);
+int sdrgpu_synth_sync(sdrgpu_synth* h);
+int sdrgpu_synth_reset(sdrgpu_synth* h);
+int sdrgpu_synth_clone(const sdrgpu_synth* h, sdrgpu_synth** out);
+void sdrgpu_synth_destroy(sdrgpu_synth* h);
 
 /* =====================================================================================
  * FFT.

@@ -368,6 +368,79 @@ impl Drop for Channelizer {
     }
 }
 
+// -------------------------------------------------------------------- synthesizer
+
+/// `nch` channel rows back into one wideband `Complex<f32>` stream (include/sdrgpu.h
+/// `sdrgpu_synth`), the way back from `Channelizer`; the reference crate has no counterpart.
+/// Row k is un-rotated by `exp(+j 2 pi k (m+1) / oversample)`, zero-stuffed by
+/// `interp = nch / oversample`, filtered with `taps[n] * exp(-j 2 pi k (L-n) / nch)` and the rows
+/// are summed, unscaled: `n` frames per channel give exactly `n * interp` samples, and any
+/// partition of the frame stream into calls gives the same samples.
+pub struct Synthesizer {
+    h: *mut sys::sdrgpu_synth,
+    nch: usize,
+}
+
+unsafe impl Send for Synthesizer {}
+
+impl Synthesizer {
+    pub fn new(taps: &[f32], nch: usize) -> Result<Self> {
+        Self::with_oversample(taps, nch, 1)
+    }
+
+    /// `nch`: a power of two, 2..4096; `oversample` 1, 2 or 4, at most `nch`;
+    /// `ceil(taps.len() / interp) <= 64`.
+    pub fn with_oversample(taps: &[f32], nch: usize, oversample: u32) -> Result<Self> {
+        let mut h = ptr::null_mut();
+        check(unsafe {
+            sys::sdrgpu_synth_create(DEVICE, taps.as_ptr(), taps.len(), nch, oversample, &mut h)
+        })?;
+        Ok(Synthesizer { h, nch })
+    }
+
+    /// Output samples per frame, `nch / oversample`.
+    pub fn interp(&self) -> usize {
+        let mut d = 0;
+        check(unsafe { sys::sdrgpu_synth_get_interp(self.h, &mut d) }).expect("sdrgpu_synth_get_interp");
+        d
+    }
+
+    /// `rows`: `nch` rows of `frames` samples each (leading dimension `frames`), the layout
+    /// `Channelizer::process` leaves; `output` gets the `frames * interp` samples.
+    pub fn process(&mut self, rows: &[Complex<f32>], frames: usize,
+                   output: &mut Vec<Complex<f32>>) -> Result<usize> {
+        assert_eq!(rows.len(), self.nch * frames);
+        let mut n = 0;
+        check(unsafe { sys::sdrgpu_synth_output_len(self.h, frames, &mut n) })?;
+        output.resize(n.max(1), Complex::new(0.0, 0.0));
+        check(unsafe {
+            sys::sdrgpu_synth_process(self.h, rows.as_ptr() as *const _, frames.max(1), frames,
+                                      output.as_mut_ptr() as *mut _, n.max(1), &mut n)
+        })?;
+        output.truncate(n);
+        Ok(n)
+    }
+
+    pub fn reset(&mut self) -> Result<()> {
+        check(unsafe { sys::sdrgpu_synth_reset(self.h) })
+    }
+}
+
+impl Clone for Synthesizer {
+    // the copy carries the oversampling, the frame count and the history
+    fn clone(&self) -> Self {
+        let mut h = ptr::null_mut();
+        check(unsafe { sys::sdrgpu_synth_clone(self.h, &mut h) }).expect("sdrgpu_synth_clone");
+        Synthesizer { h, nch: self.nch }
+    }
+}
+
+impl Drop for Synthesizer {
+    fn drop(&mut self) {
+        unsafe { sys::sdrgpu_synth_destroy(self.h) }
+    }
+}
+
 // ------------------------------------------------------------------ biquad designs
 
 /// The filter designs the PLL and the biquad stage take: `BiquadD` (src/filter/biquad.rs:

@@ -1,5 +1,6 @@
 // chan_kernels.hpp -- internal launch interface of the polyphase channelizer (chan.hip:
-// power-of-two channel counts; chan_gen.hip: any count whose prime factors are at most 13).
+// power-of-two channel counts; chan_gen.hip: any count whose prime factors are at most 13) and
+// of the synthesis bank (chan_syn.hip).
 #pragma once
 
 #include "common.hpp"
@@ -61,5 +62,36 @@ struct ChanGenPlan {
 bool chan_gen_plan(size_t M, ChanGenPlan& plan);
 // a.tw: W_M (twiddles(M)) on the device
 int chan_gen_launch(const ChanGenPlan& plan, int sample_kind, ChanArgs a, hipStream_t s);
+
+// Synthesis bank (chan_syn.hip): one block of nframes frames per channel row into nframes*D
+// samples, D = M / os.  The handle keeps the last HQ = Q - 1 frames of every row, Q = P*os (zero
+// before the stream start).  With the block appended, frame j >= 0 of row k is in[k*ld_in + j]
+// and frame j < 0 is hist[k*HQ + HQ + j]; sample o of the block sums frames o/D - HQ .. o/D.
+struct SynthArgs {
+    const float2* in;      // in[k*ld_in + j]; gaps between rows are not read
+    long ld_in;
+    long nframes;
+    const float2* hist;    // M*HQ frames, row-major
+    float2* hist_next;     // M*HQ: the history after this block (another buffer than hist)
+    long HQ;
+    int Q;                 // frames that reach one sample: P*os
+    int os;                // oversampling factor: 1, 2 or 4, at most M
+    int rot0;              // (frames before this block + 1) % os: the phase of rot(k, m)
+    int lneg;              // (-ntaps) mod M: frame m's tap n reads w_m[(n + lneg) mod M]
+    const float* taps;     // Q*D = P*M: the prototype, zero past the last tap
+    const float2* tw;      // W_4096 (fft_tile.hpp: tile_twiddles)
+    float2* out;           // n_out samples, dense
+    long n_out;            // nframes * D
+    unsigned ntiles;       // workgroups that compute samples; the ones after them carry the history
+};
+
+inline bool synth_block_ok(int M, const SynthArgs& a) {
+    if (!chan_os_ok((size_t)M, (unsigned)a.os) || a.os > M || a.Q < a.os || a.Q % a.os) return false;
+    if (a.HQ != a.Q - 1 || a.rot0 < 0 || a.rot0 >= a.os || a.lneg < 0 || a.lneg >= M) return false;
+    return a.nframes > 0 && a.ld_in >= a.nframes && a.n_out == a.nframes * (M / a.os);
+}
+
+// one launch: samples, then the history carry
+int synth_launch(int M, SynthArgs a, hipStream_t s);
 
 }  // namespace sdrgpu

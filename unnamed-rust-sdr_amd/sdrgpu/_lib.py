@@ -149,6 +149,20 @@ SIGNATURES = [
     ("sdrgpu_chan_reset", c_int, [_H]),
     ("sdrgpu_chan_clone", c_int, [_H, _PH]),
     ("sdrgpu_chan_destroy", None, [_H]),
+    # polyphase synthesis bank
+    ("sdrgpu_synth_create", c_int, [c_int, c_void_p, c_size_t, c_size_t, c_uint32, _PH]),
+    ("sdrgpu_synth_get_interp", c_int, [_H, _PS]),
+    ("sdrgpu_synth_set_stream", c_int, [_H, c_void_p]),
+    ("sdrgpu_synth_get_stream", c_int, [_H, _PH]),
+    ("sdrgpu_synth_output_len", c_int, [_H, c_size_t, _PS]),
+    ("sdrgpu_synth_process", c_int,
+     [_H, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, _PS]),
+    ("sdrgpu_synth_process_dev", c_int,
+     [_H, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, _PS]),
+    ("sdrgpu_synth_sync", c_int, [_H]),
+    ("sdrgpu_synth_reset", c_int, [_H]),
+    ("sdrgpu_synth_clone", c_int, [_H, _PH]),
+    ("sdrgpu_synth_destroy", None, [_H]),
     # FFT
     ("sdrgpu_fft_plan", c_int, [c_int, c_size_t, _PH]),
     ("sdrgpu_fft_set_stream", c_int, [_H, c_void_p]),

@@ -393,6 +393,98 @@ class Channelizer:
         check(lib().sdrgpu_chan_sync(self._h), "sdrgpu_chan_sync")
 
 
+# ---------------------------------------------------------------------- Synthesizer
+class Synthesizer:
+    """Polyphase synthesis bank: nch channel rows back into one wideband stream, the way back
+    from Channelizer (no reference counterpart; the definition is in include/sdrgpu.h).  Row k
+    is un-rotated by conj(exp(-2j*pi*k*(m+1)/oversample)), zero-stuffed by interp = nch /
+    oversample, filtered with f_k[n] = taps[n] * exp(-2j*pi*k*(L-n)/nch) and the rows are summed,
+    unscaled: n frames per channel give exactly n*interp samples.  nch: a power of two, 2..4096;
+    oversample 1, 2 or 4 (<= nch); ceil(len(taps) / interp) <= 64.  Rows and output are C64."""
+
+    def __init__(self, taps, nch: int, oversample: int = 1, device: int = 0, _handle=None):
+        taps = np.asarray(taps)
+        if np.iscomplexobj(taps) or taps.ndim != 1:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Synthesizer: taps must be a real 1-D array")
+        self.taps = _as_c(taps, F32)
+        self.nch = nch
+        self.oversample = oversample
+        self.device = device
+        self._h = ctypes.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            if not 0 <= oversample < 1 << 32:
+                raise _lib.SdrGpuError(_lib.ERR_INVALID, "Synthesizer: oversample out of range")
+            check(lib().sdrgpu_synth_create(device, self.taps.ctypes.data, self.taps.size, nch,
+                                            oversample, ctypes.byref(self._h)), "sdrgpu_synth_create")
+
+    def close(self):
+        if self._h:
+            lib().sdrgpu_synth_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clone(self) -> "Synthesizer":
+        h = ctypes.c_void_p()
+        check(lib().sdrgpu_synth_clone(self._h, ctypes.byref(h)), "sdrgpu_synth_clone")
+        return Synthesizer(self.taps, self.nch, self.oversample, self.device, _handle=h)
+
+    def reset(self):
+        check(lib().sdrgpu_synth_reset(self._h), "sdrgpu_synth_reset")
+
+    def set_stream(self, stream_ptr: Optional[int]):
+        check(lib().sdrgpu_synth_set_stream(self._h, stream_ptr), "sdrgpu_synth_set_stream")
+
+    def stream(self) -> int:
+        s = ctypes.c_void_p()
+        check(lib().sdrgpu_synth_get_stream(self._h, ctypes.byref(s)), "sdrgpu_synth_get_stream")
+        return s.value or 0
+
+    @property
+    def interp(self) -> int:
+        """Output samples per frame, nch / oversample."""
+        d = ctypes.c_size_t()
+        check(lib().sdrgpu_synth_get_interp(self._h, ctypes.byref(d)), "sdrgpu_synth_get_interp")
+        return d.value
+
+    def output_len(self, n_frames: int) -> int:
+        """Samples a process() call of n_frames frames per channel produces: n_frames * interp."""
+        n = ctypes.c_size_t()
+        check(lib().sdrgpu_synth_output_len(self._h, n_frames, ctypes.byref(n)), "output_len")
+        return n.value
+
+    def process(self, s) -> np.ndarray:
+        """s: (nch, n) host channel rows -> (n * interp,) complex64."""
+        s = np.asarray(s)
+        if s.ndim != 2 or s.shape[0] != self.nch:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, f"Synthesizer: rows must be ({self.nch}, n)")
+        s = _as_c(s, C64)
+        n = s.shape[1]
+        out = np.empty(max(self.output_len(n), 1), dtype=np.complex64)
+        got = ctypes.c_size_t()
+        check(lib().sdrgpu_synth_process(self._h, s.ctypes.data, max(n, 1), n, out.ctypes.data,
+                                         out.size, ctypes.byref(got)), "sdrgpu_synth_process")
+        return out[:got.value]
+
+    def process_dev(self, d_in_ptr: int, ld_in: int, n_frames: int, d_out_ptr: int,
+                    out_cap: int) -> int:
+        """Enqueue on the handle's stream with device pointers; channel k's frames are read from
+        d_in + k*ld_in samples.  Returns the number of samples written."""
+        got = ctypes.c_size_t()
+        check(lib().sdrgpu_synth_process_dev(self._h, d_in_ptr, ld_in, n_frames, d_out_ptr, out_cap,
+                                             ctypes.byref(got)), "sdrgpu_synth_process_dev")
+        return got.value
+
+    def sync(self):
+        check(lib().sdrgpu_synth_sync(self._h), "sdrgpu_synth_sync")
+
+
 # --------------------------------------------------------------------------- Biquad
 @dataclass(frozen=True)
 class BiquadD:
