@@ -60,9 +60,9 @@ def parse():
     ap.add_argument("--chan-oversample", type=int, default=1, choices=[1, 2, 4],
                     help="chan and synth: frames 1024/os apart, 1024 x os*2^16 frames")
     ap.add_argument("--chan-nch", type=int, default=1024,
-                    help="chan only: channel count N (2..4096, prime factors <= 13), prototype "
+                    help="chan and synth: channel count N (2..4096, prime factors <= 13), prototype "
                          "firwin(8*N, 1/N); not a power of two: the largest multiple of N samples "
-                         "in 2^log2n")
+                         "(synth: the largest whole number of frames) in 2^log2n")
     ap.add_argument("--no-fir-route", action="store_true",
                     help="chan only: skip timing the one-Fir-per-channel route")
     ap.add_argument("--gpus", type=int, default=1,
@@ -772,15 +772,19 @@ def bench_synth(args):
     sample); rows resident, event-timed on the handle's stream.  Spot check of the timed output
     (the last step's): 8 frames' worth of samples at the start, in the middle and at the end
     against the f64 polyphase form.  The handle streams, so the frames in front of a step are
-    the end of the step before it.  --chan-nch N: N rows with firwin(8 N, 1/N);
-    --chan-oversample and --chan-log2n (output samples) as for chan."""
+    the end of the step before it.  --chan-nch N: N rows with firwin(8 N, 1/N), any count
+    Synthesizer.create_any takes; an N that is not a power of two (the general-M kernel,
+    DESIGN.md 3.4b) takes the largest whole number of frames, a multiple of the oversampling,
+    whose output fits 2^log2n.  --chan-oversample and --chan-log2n (output samples) as for chan."""
     import scipy.signal as ss
     import sdrgpu
     from sdrgpu.device import DeviceBuffer, synchronize
     M, n, osf = args.chan_nch, 1 << args.chan_log2n, args.chan_oversample
-    assert M & (M - 1) == 0 and osf <= M, "--chan-nch: a power of two, at least --chan-oversample"
+    assert M % osf == 0, "--chan-oversample must divide --chan-nch"
     D = M // osf
     L, frames = 8 * M, n // D
+    frames -= frames % osf  # every step starts at a frame count that is a multiple of os
+    n = frames * D          # 2^log2n for a power of two
     Q = L // M * osf
     assert frames % osf == 0 and frames >= Q + 8
     g = ss.firwin(L, 1.0 / M).astype(np.float32)
@@ -789,7 +793,7 @@ def bench_synth(args):
     rows, y = DeviceBuffer.empty(M * frames), DeviceBuffer.empty(n)
     fill(rows, M * frames, 33)
     pat = cplx_pattern(pat_n, 33)
-    sy = sdrgpu.Synthesizer(g, M, oversample=osf)
+    sy = sdrgpu.Synthesizer.create_any(g, M, oversample=osf)
 
     def step():
         assert sy.process_dev(rows.ptr, frames, frames, y.ptr, n) == n
@@ -806,7 +810,7 @@ def bench_synth(args):
         worst = max(worst, float(np.abs(got - ref).max() / np.sqrt(np.mean(np.abs(ref) ** 2))))
     assert worst <= 1e-5 or args.no_check, worst
     return {"config": f"synth: polyphase synthesis bank, {M} rows x {frames} frames, firwin({L}, 1/{M}) "
-                      f"prototype -> 2^{args.chan_log2n} c64 samples",
+                      f"prototype -> {f'2^{args.chan_log2n}' if n == 1 << args.chan_log2n else n} c64 samples",
             "metric": "complex Msamples/s (output)", "oversample": osf, "algorithmic_bytes": 8 * osf + 8,
             "value": round(n / (ms * 1e-3) / 1e6, 1), "roofline": roof(8 * osf + 8, n, ms),
             "wall_ms_per_step": round(wall * 1e3, 3), "spot_check_max_over_rms": worst}

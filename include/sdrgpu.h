@@ -317,11 +317,26 @@ void sdrgpu_chan_destroy(sdrgpu_chan* h);
  * stream.  d_out may overlap the input rows (see sdrgpu_fir_process_dev).
  * Non-finite samples: the padded taps are summed like the others, so an inf / NaN s_k[m] makes
  * every output t in [m*D, m*D + P*M) non-finite; all other outputs are bit-identical to a
- * clean run. */
+ * clean run.
+ *
+ * Any smooth channel count (sdrgpu_synth_create_any): nch = M is 2..4096 with every prime factor
+ * <= 13 -- the counts sdrgpu_chan_create_any takes, so a bank of 9, 12, 96, 100 or 1000 channels
+ * has its way back -- oversample is in {1, 2, 4} and divides nch (D = M/os a whole number of
+ * samples, so rot stays the exact power of -1 or -j above), ceil(ntaps / D) <= 64.  x^[t], the
+ * input layout with ld_in, the exactly n_frames*D samples per call, the carried state, the
+ * bit-identical partitions, reset and clone, overlapping d_out and the non-finite statement are
+ * those above with M = nch, and every other sdrgpu_synth_* function takes the handle.  Null or
+ * zero arguments and oversample 0 are SDRGPU_ERR_INVALID; a prime factor above 13, nch 1 or
+ * above 4096, an oversample that does not divide nch or is not 1, 2 or 4, and too many taps are
+ * SDRGPU_ERR_UNSUPPORTED, all before the device is looked at.  For a power-of-two nch the call
+ * is sdrgpu_synth_create (same kernels, bit-identical outputs).  sdrgpu_synth_create keeps its
+ * contract: it takes power-of-two nch only, any other nch is SDRGPU_ERR_UNSUPPORTED. */
 typedef struct sdrgpu_synth sdrgpu_synth;
 
 int sdrgpu_synth_create(int device, const float* taps, size_t ntaps, size_t nch,
                         uint32_t oversample, sdrgpu_synth** out);
+int sdrgpu_synth_create_any(int device, const float* taps, size_t ntaps, size_t nch,
+                            uint32_t oversample, sdrgpu_synth** out);
 int sdrgpu_synth_get_interp(const sdrgpu_synth* h, size_t* interp);   /* D */
 int sdrgpu_synth_set_stream(sdrgpu_synth* h, void* hip_stream);
 int sdrgpu_synth_get_stream(const sdrgpu_synth* h, void** hip_stream);

@@ -388,12 +388,19 @@ impl Synthesizer {
         Self::with_oversample(taps, nch, 1)
     }
 
-    /// `nch`: a power of two, 2..4096; `oversample` 1, 2 or 4, at most `nch`;
-    /// `ceil(taps.len() / interp) <= 64`.
+    /// `nch`: 2..4096 with every prime factor <= 13, the counts `Channelizer` takes;
+    /// `oversample` 1, 2 or 4, a divisor of `nch`; `ceil(taps.len() / interp) <= 64`.
+    /// A power-of-two `nch` goes through `sdrgpu_synth_create`, any other count through
+    /// `sdrgpu_synth_create_any`.
     pub fn with_oversample(taps: &[f32], nch: usize, oversample: u32) -> Result<Self> {
         let mut h = ptr::null_mut();
         check(unsafe {
-            sys::sdrgpu_synth_create(DEVICE, taps.as_ptr(), taps.len(), nch, oversample, &mut h)
+            if nch.is_power_of_two() {
+                sys::sdrgpu_synth_create(DEVICE, taps.as_ptr(), taps.len(), nch, oversample, &mut h)
+            } else {
+                sys::sdrgpu_synth_create_any(DEVICE, taps.as_ptr(), taps.len(), nch, oversample,
+                                             &mut h)
+            }
         })?;
         Ok(Synthesizer { h, nch })
     }

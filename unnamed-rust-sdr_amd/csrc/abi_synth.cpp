@@ -3,7 +3,9 @@
 // counterpart; the definition is in the header.  Stream state -- the last Q - 1 = P*os - 1 frames
 // of every channel row and the frame count -- is carried on the device across calls, so block
 // partitioning never changes the outputs (chan_syn.hip computes every sample with the same
-// arithmetic wherever it falls).
+// arithmetic wherever it falls).  A channel count that is not a power of two
+// (sdrgpu_synth_create_any) runs chan_syn_gen.hip on the mixed-radix tile engine, with the tile
+// plan and the W_M table made here at create; everything else of the handle is the same.
 #include <algorithm>
 #include <new>
 #include <vector>
@@ -22,6 +24,8 @@ struct sdrgpu_synth {
     int device = 0;
     int M = 2, P = 1;
     int os = 1;                              // oversampling factor; a frame is D = M / os samples
+    bool general = false;                    // M is not a power of two: chan_syn_gen.hip, `gen`, d_tw = W_M
+    SynthGenPlan gen;
     std::vector<float> taps;                 // as given (clone)
     float* d_taps = nullptr;                 // P*M, zero past the last tap
     float2* d_tw = nullptr;
@@ -61,10 +65,12 @@ struct sdrgpu_synth {
         return SDRGPU_OK;
     }
 
-    int init(int dev, const float* g, size_t ntaps, size_t nch, uint32_t oversample) {
+    // any_m: take every channel count synth_gen_plan has a tile for, not only the powers of two
+    int init(int dev, const float* g, size_t ntaps, size_t nch, uint32_t oversample, bool any_m) {
         if (!g || ntaps == 0 || nch == 0 || oversample == 0) return SDRGPU_ERR_INVALID;
-        if (!chan_size_ok(nch)) return SDRGPU_ERR_UNSUPPORTED;
+        general = !chan_size_ok(nch);
         if (!chan_os_ok(nch, oversample) || oversample > nch) return SDRGPU_ERR_UNSUPPORTED;
+        if (general && !(any_m && synth_gen_plan(nch, oversample, gen))) return SDRGPU_ERR_UNSUPPORTED;
         const size_t d = nch / oversample;
         if ((ntaps + d - 1) / d > kSynthMaxReach) return SDRGPU_ERR_UNSUPPORTED;
         int st = check_device(dev);
@@ -80,7 +86,7 @@ struct sdrgpu_synth {
         if ((st = stream.create())) return st;
         std::vector<float> padded((size_t)P * M, 0.0f);
         std::copy(g, g + ntaps, padded.begin());
-        const std::vector<float2> tw = fftd::tile_twiddles();
+        const std::vector<float2> tw = general ? twiddles(M) : fftd::tile_twiddles();
         SDRGPU_HIP_TRY(hipMalloc(&d_taps, padded.size() * sizeof(float)));
         SDRGPU_HIP_TRY(hipMemcpy(d_taps, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice));
         SDRGPU_HIP_TRY(hipMalloc(&d_tw, tw.size() * sizeof(float2)));
@@ -122,7 +128,8 @@ struct sdrgpu_synth {
         a.tw = d_tw;
         a.out = static_cast<float2*>(d_out);
         a.n_out = (long)n_out;
-        if (int st = synth_launch(M, a, stream.cur)) return st;
+        if (int st = general ? synth_gen_launch(gen, a, stream.cur) : synth_launch(M, a, stream.cur))
+            return st;
         cur ^= 1;
         frames += n;
         return SDRGPU_OK;
@@ -147,7 +154,7 @@ struct sdrgpu_synth {
     }
 
     int clone_into(sdrgpu_synth* dst) const {
-        int st = dst->init(device, taps.data(), taps.size(), (size_t)M, (uint32_t)os);
+        int st = dst->init(device, taps.data(), taps.size(), (size_t)M, (uint32_t)os, general);
         if (st) return st;
         DeviceGuard g(device);
         dst->frames = frames;
@@ -193,7 +200,14 @@ extern "C" {
 
 int sdrgpu_synth_create(int device, const float* taps, size_t ntaps, size_t nch, uint32_t oversample,
                         sdrgpu_synth** out) {
-    return make_handle(out, [&](sdrgpu_synth* h) { return h->init(device, taps, ntaps, nch, oversample); });
+    return make_handle(out,
+                       [&](sdrgpu_synth* h) { return h->init(device, taps, ntaps, nch, oversample, false); });
+}
+
+int sdrgpu_synth_create_any(int device, const float* taps, size_t ntaps, size_t nch,
+                            uint32_t oversample, sdrgpu_synth** out) {
+    return make_handle(out,
+                       [&](sdrgpu_synth* h) { return h->init(device, taps, ntaps, nch, oversample, true); });
 }
 
 int sdrgpu_synth_get_interp(const sdrgpu_synth* h, size_t* interp) {

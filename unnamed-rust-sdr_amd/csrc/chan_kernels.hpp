@@ -1,6 +1,7 @@
 // chan_kernels.hpp -- internal launch interface of the polyphase channelizer (chan.hip:
 // power-of-two channel counts; chan_gen.hip: any count whose prime factors are at most 13) and
-// of the synthesis bank (chan_syn.hip).
+// of the synthesis bank (chan_syn.hip: power-of-two channel counts; chan_syn_gen.hip: the same
+// general counts).
 #pragma once
 
 #include "common.hpp"
@@ -79,7 +80,7 @@ struct SynthArgs {
     int rot0;              // (frames before this block + 1) % os: the phase of rot(k, m)
     int lneg;              // (-ntaps) mod M: frame m's tap n reads w_m[(n + lneg) mod M]
     const float* taps;     // Q*D = P*M: the prototype, zero past the last tap
-    const float2* tw;      // W_4096 (fft_tile.hpp: tile_twiddles)
+    const float2* tw;      // synth_launch: W_4096 (fft_tile.hpp: tile_twiddles); synth_gen_launch: W_M
     float2* out;           // n_out samples, dense
     long n_out;            // nframes * D
     unsigned ntiles;       // workgroups that compute samples; the ones after them carry the history
@@ -93,5 +94,23 @@ inline bool synth_block_ok(int M, const SynthArgs& a) {
 
 // one launch: samples, then the history carry
 int synth_launch(int M, SynthArgs a, hipStream_t s);
+
+// General M (chan_syn_gen.hip): the tile of a synthesis bank of M channels at one oversampling
+// factor, made once per handle.  A workgroup owns 16 output samples per lane and transforms
+// F = floor(tile / M) whole frames per round; tile points at or past F*M are idle.
+struct SynthGenPlan {
+    int M = 0;
+    int os = 1;
+    int tile = 0;        // points per LDS tile: 4096 (256 lanes) or 16384 (512 lanes)
+    int F = 0;           // frames per round
+    int pitch = 0;       // of the [frame][channel] image the transposed load writes
+    fftd::FastDiv df;    // F
+    fftd::FastDiv dd;    // D = M / os
+    fftd::RadixList rl;  // radices(M); rl.dn divides by M
+};
+// false unless M is 2..4096 with every prime factor <= 13 and os in {1, 2, 4} divides M
+bool synth_gen_plan(size_t M, unsigned os, SynthGenPlan& plan);
+// a.tw: W_M (twiddles(M)) on the device
+int synth_gen_launch(const SynthGenPlan& plan, SynthArgs a, hipStream_t s);
 
 }  // namespace sdrgpu

@@ -151,6 +151,7 @@ SIGNATURES = [
     ("sdrgpu_chan_destroy", None, [_H]),
     # polyphase synthesis bank
     ("sdrgpu_synth_create", c_int, [c_int, c_void_p, c_size_t, c_size_t, c_uint32, _PH]),
+    ("sdrgpu_synth_create_any", c_int, [c_int, c_void_p, c_size_t, c_size_t, c_uint32, _PH]),
     ("sdrgpu_synth_get_interp", c_int, [_H, _PS]),
     ("sdrgpu_synth_set_stream", c_int, [_H, c_void_p]),
     ("sdrgpu_synth_get_stream", c_int, [_H, _PH]),

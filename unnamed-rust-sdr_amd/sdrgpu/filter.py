@@ -392,6 +392,11 @@ class Channelizer:
     def sync(self):
         check(lib().sdrgpu_chan_sync(self._h), "sdrgpu_chan_sync")
 
+    def synthesizer(self, taps) -> "Synthesizer":
+        """The synthesis bank of this channelizer's nch, oversample and device with the
+        prototype `taps`: the way back from its rows."""
+        return Synthesizer.create_any(taps, self.nch, self.oversample, self.device)
+
 
 # ---------------------------------------------------------------------- Synthesizer
 class Synthesizer:
@@ -399,8 +404,27 @@ class Synthesizer:
     from Channelizer (no reference counterpart; the definition is in include/sdrgpu.h).  Row k
     is un-rotated by conj(exp(-2j*pi*k*(m+1)/oversample)), zero-stuffed by interp = nch /
     oversample, filtered with f_k[n] = taps[n] * exp(-2j*pi*k*(L-n)/nch) and the rows are summed,
-    unscaled: n frames per channel give exactly n*interp samples.  nch: a power of two, 2..4096;
-    oversample 1, 2 or 4 (<= nch); ceil(len(taps) / interp) <= 64.  Rows and output are C64."""
+    unscaled: n frames per channel give exactly n*interp samples.  The constructor takes nch a
+    power of two, 2..4096 (sdrgpu_synth_create); Synthesizer.create_any takes every nch 2..4096
+    whose prime factors are at most 13 (9, 12, 96, 100, 1000, ...: sdrgpu_synth_create_any, the
+    counts Channelizer takes), and Channelizer.synthesizer(taps) makes the bank that matches a
+    channelizer.  oversample 1, 2 or 4, a divisor of nch; ceil(len(taps) / interp) <= 64.  Rows
+    and output are C64."""
+
+    @classmethod
+    def create_any(cls, taps, nch: int, oversample: int = 1, device: int = 0) -> "Synthesizer":
+        """A bank of any channel count sdrgpu_synth_create_any takes; for a power of two it is
+        the constructor's."""
+        taps = np.asarray(taps)
+        if np.iscomplexobj(taps) or taps.ndim != 1:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Synthesizer: taps must be a real 1-D array")
+        if not 0 <= oversample < 1 << 32:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Synthesizer: oversample out of range")
+        t = _as_c(taps, F32)
+        h = ctypes.c_void_p()
+        check(lib().sdrgpu_synth_create_any(device, t.ctypes.data, t.size, nch, oversample,
+                                            ctypes.byref(h)), "sdrgpu_synth_create_any")
+        return cls(t, nch, oversample, device, _handle=h)
 
     def __init__(self, taps, nch: int, oversample: int = 1, device: int = 0, _handle=None):
         taps = np.asarray(taps)
