@@ -44,7 +44,7 @@ HBM_GBS = 8000.0
 
 def parse():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="all", choices=["c1", "c3", "c4", "c5", "c2u8", "c2host", "c2pinned", "src", "ex", "fm", "chan", "synth", "all"])
+    ap.add_argument("--config", default="all", choices=["c1", "c3", "c4", "c5", "c2u8", "c2host", "c2pinned", "src", "ex", "fm", "chan", "synth", "src_rows", "all"])
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--c3-log2n", type=int, default=28)
@@ -816,6 +816,77 @@ def bench_synth(args):
             "wall_ms_per_step": round(wall * 1e3, 3), "spot_check_max_over_rms": worst}
 
 
+# ------------------------------------------------------------------------------ src_rows
+def bench_src_rows(args):
+    """The rows layout of the sample-rate converter (sdrgpu_src_process_rows_dev) against the
+    interleaved handle with channels = rows on the same samples already transposed to frames,
+    device-resident, hipEvents, state carried call to call, three alternating repetitions.  The
+    interleaved figure leaves out the two transposes a user of channel rows needs around it
+    (torch's HIP runtime cannot address this library's buffers, sdrgpu/device.py), so it is a
+    lower bound of that route.  Each shape's first call is compared bit for bit."""
+    from sdrgpu import resample
+    from sdrgpu.device import DeviceBuffer, synchronize
+    CT = resample.ConverterType
+    lines = []
+    for tag, conv, rows, nf, ratio in (("a", CT.SincBestQuality, 18, 1 << 20, 1 / 3),
+                                       ("b", CT.SincFastest, 9, 1 << 22, 0.72),
+                                       ("c", CT.SincFastest, 1024, 1 << 16, 0.36),
+                                       ("d", CT.Linear, 1024, 1 << 16, 0.36)):
+        xr = np.random.default_rng(17).standard_normal((rows, nf), dtype=np.float32)
+        x_rows = DeviceBuffer.from_numpy(xr)
+        x_frames = DeviceBuffer.from_numpy(np.ascontiguousarray(xr.T))
+        del xr
+        cap = int(nf * ratio) + 16
+        y_rows = DeviceBuffer(4 * rows * cap, dtype=np.float32)
+        y_frames = DeviceBuffer(4 * rows * cap, dtype=np.float32)
+        r = resample.SampleRateRows(conv, rows)
+        g = resample.SampleRate(conv, rows)
+        ur, gr = r.process_dev(ratio, x_rows.ptr, nf, nf, y_rows.ptr, cap, cap)
+        ug, gg = g.process_dev(ratio, x_frames.ptr, nf, y_frames.ptr, cap)
+        r.sync()
+        g.sync()
+        a = y_rows.download(rows * cap, np.float32).reshape(rows, cap)[:, :gr]
+        b = y_frames.download(rows * gg, np.float32).reshape(gg, rows)
+        equal = bool((ur, gr) == (ug, gg) and np.array_equal(np.ascontiguousarray(a.T).view(np.uint32),
+                                                             b.view(np.uint32)))
+        del a, b
+        gen = [0, 0]
+
+        def step_rows():
+            gen[0] = r.process_dev(ratio, x_rows.ptr, nf, nf, y_rows.ptr, cap, cap)[1]
+
+        def step_frames():
+            gen[1] = g.process_dev(ratio, x_frames.ptr, nf, y_frames.ptr, cap)[1]
+
+        ms_rows, ms_frames = [], []
+        for _ in range(3):
+            ms_rows.append(time_events(step_rows, r.stream(), args.steps, args.warmup,
+                                       lambda: (r.sync(), synchronize()))[1])
+            ms_frames.append(time_events(step_frames, g.stream(), args.steps, args.warmup,
+                                         lambda: (g.sync(), synchronize()))[1])
+        name = {CT.SincBestQuality: "SincBestQuality", CT.SincFastest: "SincFastest",
+                CT.Linear: "linear"}[conv]
+        line = {"config": f"src_rows ({tag}): {name} ratio {ratio:.4g}, {rows} rows x {nf} frames per call",
+                "metric": "input Msamples/s (all rows), rows layout",
+                "value": round(rows * nf / (float(np.mean(ms_rows)) * 1e-3) / 1e6, 1),
+                "rows_ms": [round(v, 4) for v in ms_rows],
+                "interleaved_ms_without_transposes": [round(v, 4) for v in ms_frames],
+                "speedup_mean": round(float(np.mean(ms_frames) / np.mean(ms_rows)), 3),
+                "output_frames": gen[0], "first_call_bit_equal": equal}
+        if conv != CT.Linear:
+            c, inc = resample.sinc_table(conv)
+            taps = 2 * (c.size - 2) / (inc * min(ratio, 1.0))
+            fl = 2 * taps * gen[0] * rows / (float(np.mean(ms_rows)) * 1e-3) / 1e12
+            line["taps_per_output"] = round(taps, 1)
+            line["roofline"] = {"bound": "fp64 issue", "achieved": round(fl, 3), "peak": 78.6,
+                                "unit": "TFLOP/s (f64 vector, AMD spec)", "frac": round(fl / 78.6, 4)}
+        else:
+            line["roofline_kernel_estimate"] = roof(12, gen[0] * rows, float(np.mean(ms_rows)))
+        lines.append(line)
+        del x_rows, x_frames, y_rows, y_frames, r, g
+    return lines
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -827,7 +898,8 @@ def main():
     for c in todo:
         r = {"c1": bench_c1, "c3": bench_c3, "c4": bench_c4, "c5": bench_c5, "c2u8": bench_c2u8,
              "c2host": bench_c2host, "c2pinned": bench_c2pinned, "src": bench_src, "ex": bench_ex,
-             "fm": bench_fm, "chan": bench_chan, "synth": bench_synth}[c](args)
+             "fm": bench_fm, "chan": bench_chan, "synth": bench_synth,
+             "src_rows": bench_src_rows}[c](args)
         for line in (r if isinstance(r, list) else [r]):
             if line is not None:
                 print(json.dumps(line), flush=True)

@@ -607,6 +607,25 @@ typedef struct sdrgpu_src_state sdrgpu_src_state;
 sdrgpu_src_state* sdrgpu_src_new(int device, int converter_type, int channels, int* error);
 int sdrgpu_src_process(sdrgpu_src_state* s, sdrgpu_src_data* data);
 int sdrgpu_src_process_dev(sdrgpu_src_state* s, sdrgpu_src_data* data);
+/* Rows layout: the blocks are channel-major rows, as the channelizer and the FIR / PLL / biquad
+ * banks read and write them.  Row r of the input starts at data_in + r * ld_in floats and holds
+ * input_frames samples; row r of the output starts at data_out + r * ld_out and has room for
+ * output_frames.  By definition a rows handle is the `channels = rows` handle above applied to
+ * the transposed arrays: the counts, the error code of every call and every output sample are
+ * the same, bit for bit, for all five converters, any partition into calls, variable ratio,
+ * the end-of-input flush, reset and clone.  reset / clone / set_ratio / set_stream /
+ * get_stream / sync / delete work as on any handle and get_channels returns `rows`.
+ * sdrgpu_src_process[_dev] on a rows handle, and the rows calls on an interleaved handle,
+ * return SDRGPU_SRC_ERR_BAD_STATE.  Checked before any state is touched: ld_in < input_frames
+ * or ld_out < output_frames -> SDRGPU_SRC_ERR_BAD_DATA; the input extent
+ * [data_in, data_in + (rows - 1) * ld_in + input_frames) meeting the output's ->
+ * SDRGPU_SRC_ERR_DATA_OVERLAP (no in-place conversion).  _rows takes HOST pointers and is
+ * synchronous, _rows_dev DEVICE pointers (counts at once, work on the handle's stream). */
+sdrgpu_src_state* sdrgpu_src_new_rows(int device, int converter_type, int rows, int* error);
+int sdrgpu_src_process_rows(sdrgpu_src_state* s, sdrgpu_src_data* data, size_t ld_in,
+                            size_t ld_out);
+int sdrgpu_src_process_rows_dev(sdrgpu_src_state* s, sdrgpu_src_data* data, size_t ld_in,
+                                size_t ld_out);
 int sdrgpu_src_sync(sdrgpu_src_state* s);
 int sdrgpu_src_reset(sdrgpu_src_state* s);
 sdrgpu_src_state* sdrgpu_src_clone(sdrgpu_src_state* s, int* error);

@@ -28,6 +28,7 @@ namespace {
 
 constexpr double kSrcMaxRatio = 256.0;           // SRC_MAX_RATIO
 constexpr double kSrcMinRatioDiff = 1e-20;       // SRC_MIN_RATIO_DIFF
+constexpr int kSrcRowsWide = 64;                 // rows handles: interleaved window from here on
 
 bool is_bad_src_ratio(double r) { return r < 1.0 / kSrcMaxRatio || r > kSrcMaxRatio; }
 
@@ -163,6 +164,15 @@ const char* const kDescriptions[5] = {
 
 struct sdrgpu_src_state {
     int device = 0, type = SDRGPU_SRC_LINEAR, channels = 1;
+    // rows handle (sdrgpu_src_new_rows): channels = rows, the same bookkeeping, but blocks and
+    // the sinc window are channel-major rows; sample indices / channels = frame indices
+    bool planar = false;
+    long wld[2] = {0, 0};  // frames per window row of win[0] / win[1]
+    // From kSrcRowsWide rows on, a rows handle keeps the window channel-interleaved, as the
+    // wide-frame sinc kernel reads it (one frame x 256 channels per workgroup, coalesced
+    // over the channels): the appends transpose the input rows into it and the kernel stores
+    // along the output rows.  Below that the window is planar (resample_rows.hip).
+    bool win_rows() const { return planar && channels < kSrcRowsWide; }
     // SRC_STATE + LINEAR_DATA / ZOH_DATA (host side; last_value lives on the device)
     double last_position = 0.0, last_ratio = 0.0;
     bool reset_pending = true;
@@ -203,10 +213,11 @@ struct sdrgpu_src_state {
         stage_out.release();
         stream.destroy();
     }
-    int init(int dev, int typ, int ch) {
+    int init(int dev, int typ, int ch, bool rows_layout) {
         device = dev;
         type = typ;
         channels = ch;
+        planar = rows_layout;
         DeviceGuard g(device);
         if (!g.ok()) return SDRGPU_SRC_ERR_BAD_STATE;
         if (stream.create()) return SDRGPU_SRC_ERR_BAD_STATE;
@@ -345,6 +356,32 @@ struct sdrgpu_src_state {
         return 0;
     }
 
+    // sinc_window for a rows handle, in frames.  Every index the bookkeeping moves the window
+    // by (voff: b_current - half, both multiples of the channel count) is a whole frame; only
+    // vend can be ragged, after the end-of-input tail, which is rounded up to whole frames.
+    int sinc_window_rows(long need_more) {
+        const long ch = channels;
+        const long live = (vend - voff + ch - 1) / ch, used = (vend - vlo + ch - 1) / ch;
+        if (used + need_more <= wld[wcur]) return 0;
+        const long want = (live + need_more) * 2;
+        const int nx = wcur ^ 1;
+        if (wld[nx] < want) {
+            if (hipStreamSynchronize(stream.cur) != hipSuccess) return SDRGPU_SRC_ERR_BAD_STATE;
+            wld[nx] = 0;
+            if (win[nx].ensure((size_t)want * (size_t)ch * sizeof(float)))
+                return SDRGPU_SRC_ERR_MALLOC_FAILED;
+            wld[nx] = want;
+        }
+        if (live > 0 &&
+            src_rows_copy_launch(static_cast<float*>(win[nx].ptr), wld[nx],
+                                 static_cast<const float*>(win[wcur].ptr) + (voff - vlo) / ch,
+                                 wld[wcur], channels, live, stream.cur))
+            return SDRGPU_SRC_ERR_BAD_STATE;
+        wcur = nx;
+        vlo = voff;
+        return 0;
+    }
+
     // buffer samples [b_end, b_end + len) become input samples [src, src + len) (src = -1:
     // zeros) -- libsamplerate's memcpy / memset into its buffer
     int sinc_append(long src, long len) {
@@ -398,9 +435,34 @@ struct sdrgpu_src_state {
     }
 
     // the buffer fills recorded by sinc_append, in order: input copies and zero runs
-    int flush_appends(const float* d_in) {
+    int flush_appends(const float* d_in, size_t ld_in) {
         float* w = static_cast<float*>(win[wcur].ptr);
+        if (win_rows()) {
+            // whole frames per row.  The zero tail of the end of input (half + 5 samples) is
+            // the one append that is not: it is rounded up to whole zero frames.  No tap
+            // reads the difference: an output needs b_current < b_real_end, so its last right
+            // tap is below sample b_real_end + half, a frame boundary inside the tail.
+            const long ch = channels;
+            int st = 0;
+            for (const Append& a : appends) {
+                if (a.wpos % ch || (a.src > 0 && a.src % ch)) st = SDRGPU_SRC_ERR_BAD_INTERNAL_STATE;
+                if (st) break;
+                if (src_rows_copy_launch(w + a.wpos / ch, wld[wcur],
+                                         a.src < 0 ? nullptr : d_in + a.src / ch, (long)ld_in,
+                                         channels, (a.len + ch - 1) / ch, stream.cur))
+                    st = SDRGPU_SRC_ERR_BAD_STATE;
+            }
+            appends.clear();
+            return st;
+        }
         for (const Append& a : appends) {
+            if (planar && a.src >= 0) {  // input rows into the interleaved window
+                if (a.src % channels || a.len % channels) return SDRGPU_SRC_ERR_BAD_INTERNAL_STATE;
+                if (src_rows_to_frames_launch(w + a.wpos, d_in + a.src / channels, (long)ld_in,
+                                              channels, a.len / channels, stream.cur))
+                    return SDRGPU_SRC_ERR_BAD_STATE;
+                continue;
+            }
             hipError_t e = a.src < 0
                 ? hipMemsetAsync(w + a.wpos, 0, (size_t)a.len * sizeof(float), stream.cur)
                 : hipMemcpyAsync(w + a.wpos, d_in + a.src, (size_t)a.len * sizeof(float),
@@ -413,7 +475,8 @@ struct sdrgpu_src_state {
 
     // src_sinc.c's multichannel vari process loop; per output frame a descriptor of
     // calc_output_multi's taps (the samples are summed on the GPU, resample.hip)
-    int sinc_process(sdrgpu_src_data& d, const float* d_in, bool in_null, float* d_out) {
+    int sinc_process(sdrgpu_src_data& d, const float* d_in, bool in_null, float* d_out,
+                     size_t ld_in, size_t ld_out) {
         const int ch = channels;
         const long in_count = d.input_frames * ch, out_count = d.output_frames * ch;
         long in_used = 0, out_gen = 0;
@@ -433,7 +496,11 @@ struct sdrgpu_src_state {
         // this call appends at most its input, the lead-in zeros and the end-of-input tail
         // (2 half + 5 <= b_len); window indices are int
         if (in_count + 2L * b_len > (long)(INT32_MAX / 2)) return SDRGPU_SRC_ERR_BAD_DATA;
-        if (int st = sinc_window(in_count + (long)b_len + 16)) return st;
+        if (int st = win_rows() ? sinc_window_rows((in_count + (long)b_len) / ch + 16)
+                            : sinc_window(in_count + (long)b_len + 16))
+            return st;
+        // input frames one output frame advances by, at most (the rows kernel's tiling)
+        const long step = rmin < 1.0 ? (long)std::ceil(1.0 / rmin) : 1;
         const size_t cap_frames = max_out_frames(d);
         PinnedBytes& hb = desc_host[slot];
         if (hb.ensure(cap_frames * sizeof(SincDesc) + sizeof(SincDesc)))
@@ -445,7 +512,7 @@ struct sdrgpu_src_state {
         // (as libsamplerate, which has already copied the data by then): enqueue the appends
         // recorded so far so the device window matches that bookkeeping before returning
         auto fail = [&](int st) {
-            (void)flush_appends(d_in);
+            (void)flush_appends(d_in, ld_in);
             return st;
         };
         while (out_gen < out_count) {
@@ -494,8 +561,12 @@ struct sdrgpu_src_state {
         }
         last_position = input_index;
         last_ratio = src_ratio;
+        // rows: the kernel divides the descriptors' sample indices by ch into frame indices of
+        // a window row; every index the loop above moved is a whole number of frames
+        if (win_rows() && (b_current % ch || voff % ch || vlo % ch))
+            return fail(SDRGPU_SRC_ERR_BAD_INTERNAL_STATE);
         // enqueue: the buffer fills (input copies / zeros), the descriptors, the sums
-        if (int st = flush_appends(d_in)) return st;
+        if (int st = flush_appends(d_in, ld_in)) return st;
         float* w = static_cast<float*>(win[wcur].ptr);
         if (k > 0) {
             if (d_desc.ensure((size_t)k * sizeof(SincDesc))) return SDRGPU_SRC_ERR_MALLOC_FAILED;
@@ -505,9 +576,16 @@ struct sdrgpu_src_state {
                 return SDRGPU_SRC_ERR_BAD_STATE;
             hb.pending = true;
             slot ^= 1;
-            if (src_sinc_launch(w, ch, static_cast<const SincDesc*>(d_desc.ptr), k,
-                                static_cast<const float*>(d_coeffs.ptr), coeff_half_len + 2, d_out,
-                                stream.cur))
+            if (win_rows() ? src_sinc_rows_launch(w, wld[wcur], ch,
+                                                  static_cast<const SincDesc*>(d_desc.ptr), k, step,
+                                                  static_cast<const float*>(d_coeffs.ptr), d_out,
+                                                  (long)ld_out, stream.cur)
+                : planar ? src_sinc_rows_wide_launch(w, ch, static_cast<const SincDesc*>(d_desc.ptr),
+                                                     k, static_cast<const float*>(d_coeffs.ptr),
+                                                     d_out, (long)ld_out, stream.cur)
+                       : src_sinc_launch(w, ch, static_cast<const SincDesc*>(d_desc.ptr), k,
+                                         static_cast<const float*>(d_coeffs.ptr),
+                                         coeff_half_len + 2, d_out, stream.cur))
                 return SDRGPU_SRC_ERR_BAD_STATE;
         }
         d.input_frames_used = in_used / ch;
@@ -517,7 +595,9 @@ struct sdrgpu_src_state {
 
     // src_process after its argument checks + the converter; d_in / d_out are device
     // pointers (the host-pointer entry point passes its staging buffers).
-    int process(sdrgpu_src_data* user, const float* d_in, float* d_out, bool in_null) {
+    // A rows handle reads row r at d_in + r * ld_in and writes it at d_out + r * ld_out.
+    int process(sdrgpu_src_data* user, const float* d_in, float* d_out, bool in_null,
+                size_t ld_in = 0, size_t ld_out = 0) {
         sdrgpu_src_data& d = *user;
         d.input_frames_used = 0;
         d.output_frames_gen = 0;
@@ -525,15 +605,17 @@ struct sdrgpu_src_state {
         if (sinc()) {
             DeviceGuard g(device);
             if (!g.ok()) return SDRGPU_SRC_ERR_BAD_STATE;
-            return sinc_process(d, d_in, in_null, d_out);
+            return sinc_process(d, d_in, in_null, d_out, ld_in, ld_out);
         }
         if (d.input_frames <= 0) return 0;
         DeviceGuard g(device);
         if (!g.ok()) return SDRGPU_SRC_ERR_BAD_STATE;
         const size_t fb = sizeof(float) * (size_t)channels;
         if (reset_pending) {  // "If we have just been reset, set the last_value data."
-            if (hipMemcpyAsync(d_last_value, d_in, fb, hipMemcpyDeviceToDevice, stream.cur) !=
-                hipSuccess)
+            if (planar ? src_rows_copy_launch(d_last_value, 1, d_in, (long)ld_in, channels, 1,
+                                              stream.cur) != SDRGPU_OK
+                       : hipMemcpyAsync(d_last_value, d_in, fb, hipMemcpyDeviceToDevice,
+                                        stream.cur) != hipSuccess)
                 return SDRGPU_SRC_ERR_BAD_STATE;
             reset_pending = false;
         }
@@ -559,13 +641,18 @@ struct sdrgpu_src_state {
             if (hipEventRecord(t.done, stream.cur) != hipSuccess) return SDRGPU_SRC_ERR_BAD_STATE;
             t.pending = true;
             slot ^= 1;
-            if (src_interp_launch(linear(), d_in, channels, dl, dfr, nout, d_last_value, d_out,
-                                  stream.cur))
+            if (planar ? src_interp_rows_launch(linear(), d_in, (long)ld_in, channels, dl, dfr,
+                                                nout, d_last_value, d_out, (long)ld_out,
+                                                stream.cur)
+                       : src_interp_launch(linear(), d_in, channels, dl, dfr, nout, d_last_value,
+                                           d_out, stream.cur))
                 return SDRGPU_SRC_ERR_BAD_STATE;
         }
         if (in_used > 0 &&
-            hipMemcpyAsync(d_last_value, d_in + (in_used - channels), fb,
-                           hipMemcpyDeviceToDevice, stream.cur) != hipSuccess)
+            (planar ? src_rows_copy_launch(d_last_value, 1, d_in + (in_used / channels - 1),
+                                           (long)ld_in, channels, 1, stream.cur) != SDRGPU_OK
+                    : hipMemcpyAsync(d_last_value, d_in + (in_used - channels), fb,
+                                     hipMemcpyDeviceToDevice, stream.cur) != hipSuccess))
             return SDRGPU_SRC_ERR_BAD_STATE;
         d.input_frames_used = in_used / channels;
         d.output_frames_gen = nout;
@@ -577,7 +664,7 @@ namespace {
 
 // src_process's argument checks (samplerate.c), before any state is touched
 int check_data(const sdrgpu_src_state* s, sdrgpu_src_data* d) {
-    if (!s) return SDRGPU_SRC_ERR_BAD_STATE;
+    if (!s || s->planar) return SDRGPU_SRC_ERR_BAD_STATE;
     if (!d) return SDRGPU_SRC_ERR_BAD_DATA;
     if ((!d->data_in && d->input_frames > 0) || (!d->data_out && d->output_frames > 0))
         return SDRGPU_SRC_ERR_BAD_DATA_PTR;
@@ -594,11 +681,30 @@ int check_data(const sdrgpu_src_state* s, sdrgpu_src_data* d) {
     return 0;
 }
 
-}  // namespace
+// the same checks for the rows calls; the row ranges are [p, p + (rows - 1) * ld + frames)
+int check_rows(const sdrgpu_src_state* s, sdrgpu_src_data* d, size_t ld_in, size_t ld_out) {
+    if (!s || !s->planar) return SDRGPU_SRC_ERR_BAD_STATE;
+    if (!d) return SDRGPU_SRC_ERR_BAD_DATA;
+    if ((!d->data_in && d->input_frames > 0) || (!d->data_out && d->output_frames > 0))
+        return SDRGPU_SRC_ERR_BAD_DATA_PTR;
+    if (is_bad_src_ratio(d->src_ratio)) return SDRGPU_SRC_ERR_BAD_SRC_RATIO;
+    if (d->input_frames < 0) d->input_frames = 0;
+    if (d->output_frames < 0) d->output_frames = 0;
+    if ((size_t)d->input_frames > ld_in || (size_t)d->output_frames > ld_out)
+        return SDRGPU_SRC_ERR_BAD_DATA;
+    if (d->input_frames > (long)INT32_MAX) return SDRGPU_SRC_ERR_BAD_DATA;  // 32-bit frame ids
+    const size_t rows = (size_t)s->channels;
+    const size_t ext_in = d->input_frames ? (rows - 1) * ld_in + (size_t)d->input_frames : 0;
+    const size_t ext_out = d->output_frames ? (rows - 1) * ld_out + (size_t)d->output_frames : 0;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d->data_in);
+    const uintptr_t b = reinterpret_cast<uintptr_t>(d->data_out);
+    if (ext_in && ext_out && a < b + ext_out * sizeof(float) && b < a + ext_in * sizeof(float))
+        return SDRGPU_SRC_ERR_DATA_OVERLAP;
+    return 0;
+}
 
-extern "C" {
-
-sdrgpu_src_state* sdrgpu_src_new(int device, int converter_type, int channels, int* error) {
+sdrgpu_src_state* src_create(int device, int converter_type, int channels, bool rows_layout,
+                             int* error) {
     int dummy;
     int* err = error ? error : &dummy;
     *err = 0;
@@ -619,13 +725,70 @@ sdrgpu_src_state* sdrgpu_src_new(int device, int converter_type, int channels, i
         *err = SDRGPU_SRC_ERR_MALLOC_FAILED;
         return nullptr;
     }
-    if (int st = s->init(device, converter_type, channels)) {
+    if (int st = s->init(device, converter_type, channels, rows_layout)) {
         s->free_all();
         delete s;
         *err = st;
         return nullptr;
     }
     return s;
+}
+
+// rows x frames between a host array (row pitch ld_in / ld_out) and the compact staging rows
+int copy_rows(void* dst, size_t dld, const void* src, size_t sld, size_t frames, size_t rows,
+              hipMemcpyKind kind, hipStream_t st) {
+    if (!frames || !rows) return 0;
+    const hipError_t e =
+        dld == frames && sld == frames
+            ? hipMemcpyAsync(dst, src, rows * frames * sizeof(float), kind, st)
+            : hipMemcpy2DAsync(dst, dld * sizeof(float), src, sld * sizeof(float),
+                               frames * sizeof(float), rows, kind, st);
+    return e == hipSuccess ? 0 : SDRGPU_SRC_ERR_BAD_STATE;
+}
+
+}  // namespace
+
+extern "C" {
+
+sdrgpu_src_state* sdrgpu_src_new(int device, int converter_type, int channels, int* error) {
+    return src_create(device, converter_type, channels, false, error);
+}
+
+sdrgpu_src_state* sdrgpu_src_new_rows(int device, int converter_type, int rows, int* error) {
+    return src_create(device, converter_type, rows, true, error);
+}
+
+int sdrgpu_src_process_rows_dev(sdrgpu_src_state* s, sdrgpu_src_data* d, size_t ld_in,
+                                size_t ld_out) {
+    if (int st = check_rows(s, d, ld_in, ld_out)) return st;
+    return s->process(d, d->data_in, d->data_out, d->data_in == nullptr, ld_in, ld_out);
+}
+
+int sdrgpu_src_process_rows(sdrgpu_src_state* s, sdrgpu_src_data* d, size_t ld_in,
+                            size_t ld_out) {
+    if (int st = check_rows(s, d, ld_in, ld_out)) return st;
+    DeviceGuard g(s->device);
+    if (!g.ok()) return SDRGPU_SRC_ERR_BAD_STATE;
+    const size_t rows = (size_t)s->channels;
+    const size_t nin = (size_t)d->input_frames;
+    // compact staging rows: never more output frames than the call can produce
+    const size_t nout_max = s->max_out_frames(*d);
+    if (s->stage_in.ensure(nin * rows * sizeof(float)) ||
+        s->stage_out.ensure(nout_max * rows * sizeof(float)))
+        return SDRGPU_SRC_ERR_MALLOC_FAILED;
+    if (copy_rows(s->stage_in.ptr, nin, d->data_in, ld_in, nin, rows, hipMemcpyHostToDevice,
+                  s->stream.cur))
+        return SDRGPU_SRC_ERR_BAD_STATE;
+    float* user_out = d->data_out;
+    int st = s->process(d, static_cast<const float*>(s->stage_in.ptr),
+                        static_cast<float*>(s->stage_out.ptr), d->data_in == nullptr, nin,
+                        nout_max);
+    if (st) return st;
+    if (copy_rows(user_out, ld_out, s->stage_out.ptr, nout_max, (size_t)d->output_frames_gen,
+                  rows, hipMemcpyDeviceToHost, s->stream.cur))
+        return SDRGPU_SRC_ERR_BAD_STATE;
+    if (hipStreamSynchronize(s->stream.cur) != hipSuccess) return SDRGPU_SRC_ERR_BAD_STATE;
+    return 0;
 }
 
 int sdrgpu_src_process_dev(sdrgpu_src_state* s, sdrgpu_src_data* d) {
@@ -677,7 +840,7 @@ sdrgpu_src_state* sdrgpu_src_clone(sdrgpu_src_state* s, int* error) {
         *err = SDRGPU_SRC_ERR_BAD_STATE;
         return nullptr;
     }
-    sdrgpu_src_state* c = sdrgpu_src_new(s->device, s->type, s->channels, err);
+    sdrgpu_src_state* c = src_create(s->device, s->type, s->channels, s->planar, err);
     if (!c) return nullptr;
     c->last_position = s->last_position;
     c->last_ratio = s->last_ratio;
@@ -692,11 +855,25 @@ sdrgpu_src_state* sdrgpu_src_clone(sdrgpu_src_state* s, int* error) {
         c->vlo = s->voff;
         c->wcur = 0;
         const long live = s->vend - s->voff;
-        if (c->win[0].ensure((size_t)(live > 0 ? live : 1) * 2 * sizeof(float)) ||
-            (live > 0 &&
-             hipMemcpyAsync(c->win[0].ptr, static_cast<float*>(s->win[s->wcur].ptr) + (s->voff - s->vlo),
-                            (size_t)live * sizeof(float), hipMemcpyDeviceToDevice,
-                            s->stream.cur) != hipSuccess)) {
+        bool bad;
+        if (s->win_rows()) {  // whole frames per window row
+            const long ch = s->channels, lf = (live + ch - 1) / ch;
+            c->wld[0] = (lf > 0 ? lf : 1) * 2;
+            bad = c->win[0].ensure((size_t)c->wld[0] * (size_t)ch * sizeof(float)) ||
+                  (lf > 0 &&
+                   src_rows_copy_launch(static_cast<float*>(c->win[0].ptr), c->wld[0],
+                                        static_cast<const float*>(s->win[s->wcur].ptr) +
+                                            (s->voff - s->vlo) / ch,
+                                        s->wld[s->wcur], s->channels, lf, s->stream.cur));
+        } else {
+            bad = c->win[0].ensure((size_t)(live > 0 ? live : 1) * 2 * sizeof(float)) ||
+                  (live > 0 &&
+                   hipMemcpyAsync(c->win[0].ptr,
+                                  static_cast<float*>(s->win[s->wcur].ptr) + (s->voff - s->vlo),
+                                  (size_t)live * sizeof(float), hipMemcpyDeviceToDevice,
+                                  s->stream.cur) != hipSuccess);
+        }
+        if (bad) {
             c->free_all();
             delete c;
             *err = SDRGPU_SRC_ERR_BAD_STATE;

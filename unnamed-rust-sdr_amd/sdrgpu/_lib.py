@@ -230,6 +230,9 @@ SIGNATURES = [
     ("sdrgpu_src_new", c_void_p, [c_int, c_int, c_int, POINTER(c_int)]),
     ("sdrgpu_src_process", c_int, [_H, c_void_p]),
     ("sdrgpu_src_process_dev", c_int, [_H, c_void_p]),
+    ("sdrgpu_src_new_rows", c_void_p, [c_int, c_int, c_int, POINTER(c_int)]),
+    ("sdrgpu_src_process_rows", c_int, [_H, c_void_p, c_size_t, c_size_t]),
+    ("sdrgpu_src_process_rows_dev", c_int, [_H, c_void_p, c_size_t, c_size_t]),
     ("sdrgpu_src_sync", c_int, [_H]),
     ("sdrgpu_src_reset", c_int, [_H]),
     ("sdrgpu_src_clone", c_void_p, [_H, POINTER(c_int)]),

@@ -74,3 +74,77 @@ def receiver(rtl):
             yield np.stack([y[0] + y[1], y[0] - y[1]], axis=1)
 
     return Signal(md.rate(), out, None)
+
+
+def _convert_rows(sr, ratio, blocks):
+    """Every block of (rows, n) through `sr`, then the end-of-input flush (the sinc converters
+    are partition-invariant, so the block sizes do not change a sample)."""
+    for x in blocks:
+        x = np.ascontiguousarray(x, np.float32)
+        while x.shape[1]:
+            used, y = sr.process(ratio, x, int(x.shape[1] * ratio) + 64)
+            if y.shape[1]:
+                yield y
+            if not used and not y.shape[1]:
+                raise _lib.SdrGpuError(_lib.ERR_INVALID, "fm.receivers: the converter stalled")
+            x = x[:, used:]
+    while True:
+        _, y = sr.process(ratio, np.zeros((sr.rows(), 0), np.float32), 4096)
+        if not y.shape[1]:
+            return
+        yield y
+
+
+def receivers(wideband, nch: int, taps, oversample: int = 2):
+    """`receiver`'s chain for every channel of one wideband capture: `wideband` (c64 or rtl_tcp
+    CU8 Signal) -> Signal of (nch, n, 2) f32 blocks, (left, right) at 48 kHz for station k in
+    the band centred at +k * rate / nch.  Every stage reads and writes channel rows:
+
+      Channelizer(taps, nch, oversample)              -> (nch, n) c64 at rate * oversample / nch
+      discriminator Pll bank, None -> 0.0, / 75000    (main.rs:41-47 per row)
+      SampleRateRows(SincFastest, nch) to 144 kHz     (main.rs:48)
+      pilot Pll bank, stereo-difference output        (main.rs:54-69)
+      SampleRateRows(SincBestQuality, 2 nch) to 48 kHz over mono_0, diff_0, mono_1, ...
+      de-emphasis Biquad bank of 2 nch rows           -> (mono + diff, mono - diff)
+
+    Station k's samples are `receiver`'s stage for stage on channel row k.  oversample must be
+    one the Channelizer offers for nch (1, or 2 / 4 where they divide nch)."""
+    from .signal import Signal
+    if wideband.sample_kind not in (_lib.C64, _lib.CU8):
+        raise _lib.SdrGpuError(_lib.ERR_INVALID, "fm.receivers: expects a c64 or CU8 Signal")
+    kind = wideband.sample_kind
+    taps = np.asarray(taps, np.float32)
+    probe = _filter.Channelizer(taps, nch, sample_kind=kind, oversample=oversample)
+    row_rate = wideband.rate() / probe.decim
+    probe.close()
+    dev = np.float32(DEVIATION)
+    r1 = float(np.float32(48000.0 * 3.0)) / float(np.float32(row_rate))
+    r2 = float(np.float32(48000.0)) / float(np.float32(48000.0 * 3.0))
+
+    def fm():
+        chan = _filter.Channelizer(taps, nch, sample_kind=kind, oversample=oversample)
+        disc = discriminator_design().design(row_rate, nch=nch)
+        for b in wideband.blocks():
+            rows = chan.process(b)
+            if rows.shape[1]:
+                v, locked = disc.process(rows)
+                yield np.where(locked != 0, v, np.float32(0.0)).astype(np.float32) / dev
+
+    def stereo():
+        pilot = pilot_design().design(48000.0 * 3.0, nch=nch)
+        for a in _convert_rows(_resample.SampleRateRows(
+                _resample.ConverterType.SincFastest, nch), r1, fm()):
+            mono, diff, _ = pilot.stereo(a)
+            md = np.empty((2 * nch, a.shape[1]), np.float32)
+            md[0::2] = mono
+            md[1::2] = diff
+            yield md
+
+    def out():
+        bank = deemphasis().design(48000.0, sample_kind=_lib.F32, nch=2 * nch)
+        for md in _convert_rows(_resample.SampleRateRows(
+                _resample.ConverterType.SincBestQuality, 2 * nch), r2, stereo()):
+            y = bank.process(np.ascontiguousarray(md))
+            yield np.stack([y[0::2] + y[1::2], y[0::2] - y[1::2]], axis=2)
+
+    return Signal(48000.0, out, None)

@@ -164,3 +164,89 @@ class SampleRate:
 
     def set_ratio(self, ratio: float):
         Error.result(lib().sdrgpu_src_set_ratio(self.h, float(ratio)))
+
+
+class SampleRateRows:
+    """The converters over channel-major rows (sdrgpu_src_new_rows): blocks of shape (rows, n)
+    f32, the layout the Channelizer writes and the FirBank / Pll / Biquad banks speak.  By
+    definition it is `SampleRate(typ, rows)` applied to the transposed blocks: the same counts,
+    errors and output samples, bit for bit, with no transposes."""
+
+    def __init__(self, typ: ConverterType, rows: int, device: int = 0, _h=None):
+        self.device = device
+        self._rows = rows
+        if _h is not None:
+            self.h = _h
+            return
+        err = c_int(0)
+        self.h = lib().sdrgpu_src_new_rows(device, int(typ), rows, ctypes.byref(err))
+        if not self.h:
+            raise Error(err.value or 2)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().sdrgpu_src_delete(self.h)
+            self.h = None
+
+    def process(self, ratio: float, x, out_cap: int, out=None):
+        """x: (rows, n) f32 (a view whose rows are contiguous keeps its row stride as ld_in; an
+        empty block is the end of input) -> (input_frames_used, y of shape (rows, m)).  `out`:
+        an optional (rows, >= out_cap) f32 array with contiguous rows to convert into; y is
+        then a view of it."""
+        x = np.asarray(x, np.float32)
+        if x.ndim != 2 or x.shape[0] != self._rows:
+            raise ValueError(f"expected a block of shape ({self._rows}, n), got {x.shape}")
+        n = x.shape[1]
+        if n and (x.strides[1] != 4 or x.strides[0] % 4 or x.strides[0] < 4 * n):
+            x = np.ascontiguousarray(x)
+        ld_in = x.strides[0] // 4 if n else 0
+        cap = int(out_cap)
+        if out is None:
+            out = np.empty((self._rows, max(cap, 1)), np.float32)
+        elif (out.dtype != np.float32 or out.ndim != 2 or out.shape[0] != self._rows
+              or out.shape[1] < cap or out.strides[1] != 4 or out.strides[0] % 4):
+            raise ValueError("out: expected (rows, >= out_cap) float32 with contiguous rows")
+        d = SrcData(x.ctypes.data if n else _EMPTY.ctypes.data, out.ctypes.data, n, cap, 0, 0,
+                    1 if n == 0 else 0, float(ratio))
+        Error.result(lib().sdrgpu_src_process_rows(self.h, ctypes.byref(d), ld_in,
+                                                   out.strides[0] // 4))
+        return d.input_frames_used, out[:, :d.output_frames_gen]
+
+    def process_dev(self, ratio: float, d_in: int, ld_in: int, n: int, d_out: int, ld_out: int,
+                    out_cap: int):
+        """Device pointers: row r is read at d_in + r*ld_in floats and written at d_out +
+        r*ld_out.  Returns (input_frames_used, output_frames_gen) at once; the conversion is
+        enqueued on the handle's stream."""
+        d = SrcData(d_in or _EMPTY.ctypes.data, d_out or None, n, out_cap, 0, 0,
+                    1 if n == 0 else 0, float(ratio))
+        Error.result(lib().sdrgpu_src_process_rows_dev(self.h, ctypes.byref(d), ld_in, ld_out))
+        return d.input_frames_used, d.output_frames_gen
+
+    def set_stream(self, stream_ptr):
+        Error.result(lib().sdrgpu_src_set_stream(self.h, stream_ptr))
+
+    def stream(self) -> int:
+        p = c_void_p()
+        Error.result(lib().sdrgpu_src_get_stream(self.h, ctypes.byref(p)))
+        return p.value or 0
+
+    def sync(self):
+        Error.result(lib().sdrgpu_src_sync(self.h))
+
+    def reset(self):
+        Error.result(lib().sdrgpu_src_reset(self.h))
+
+    def try_clone(self) -> "SampleRateRows":
+        err = c_int(0)
+        h = lib().sdrgpu_src_clone(self.h, ctypes.byref(err))
+        if not h:
+            raise Error(err.value or 2)
+        return SampleRateRows(ConverterType.Linear, self._rows, self.device, _h=h)
+
+    clone = try_clone
+
+    def rows(self) -> int:
+        return lib().sdrgpu_src_get_channels(self.h)
+
+    def set_ratio(self, ratio: float):
+        Error.result(lib().sdrgpu_src_set_ratio(self.h, float(ratio)))
