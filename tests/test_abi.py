@@ -59,6 +59,51 @@ def test_invalid_arguments_rejected_before_device(sdr):
     L.sdrgpu_fir_destroy(None)  # no-op like Drop on a null
 
 
+def test_null_handles_rejected_by_every_family(sdr):
+    """The lifecycle calls of the eight handle families that share the sdrgpu error codes: a NULL
+    handle is SDRGPU_ERR_INVALID, destroy(NULL) returns, a create without an out-pointer is
+    SDRGPU_ERR_INVALID.  (get_stream with a NULL out-pointer needs a live handle: not here.)"""
+    from sdrgpu import _lib
+    L = sdr.lib()
+    out = ctypes.c_void_p()
+    families = {  # name: has reset, has clone
+        "fir": (True, True), "firbank": (True, True), "chan": (True, True), "synth": (True, True),
+        "fft": (False, False), "stft": (True, False), "pll": (True, True), "biquad": (True, True),
+    }
+    for fam, (has_reset, has_clone) in families.items():
+        fn = lambda op: getattr(L, f"sdrgpu_{fam}_{op}")
+        assert fn("set_stream")(None, None) == _lib.ERR_INVALID, fam
+        assert fn("get_stream")(None, ctypes.byref(out)) == _lib.ERR_INVALID, fam
+        assert fn("sync")(None) == _lib.ERR_INVALID, fam
+        if has_reset:
+            assert fn("reset")(None) == _lib.ERR_INVALID, fam
+        if has_clone:
+            assert fn("clone")(None, ctypes.byref(out)) == _lib.ERR_INVALID, fam
+        assert fn("destroy")(None) is None, fam
+
+    taps = np.ones(4, np.float32)
+    t = taps.ctypes.data
+    pll = _lib.PllParamsC(19000.0, 1.0, 144000.0, _lib.BiquadDesignC(_lib.BQ_IDENTITY, 0.0, 0.0),
+                          _lib.BiquadDesignC(_lib.BQ_IDENTITY, 0.0, 0.0),
+                          _lib.BiquadDesignC(_lib.BQ_IDENTITY, 0.0, 0.0))
+    bq = _lib.BiquadDesignC(_lib.BQ_LOWPASS, 1000.0, 0.707)
+    creates = {
+        "fir_create": (0, _lib.C64, _lib.F32, t, 4, 1, None),
+        "firbank_create": (0, _lib.C64, _lib.F32, t, 4, 1, 2, None),
+        "chan_create": (0, _lib.C64, t, 4, 2, None),
+        "chan_create_os": (0, _lib.C64, t, 4, 2, 1, None),
+        "chan_create_any": (0, _lib.C64, t, 4, 6, 1, None),
+        "synth_create": (0, t, 4, 2, 1, None),
+        "synth_create_any": (0, t, 4, 6, 1, None),
+        "fft_plan": (0, 64, None),
+        "stft_create": (0, 64, 16, None),
+        "pll_create": (0, ctypes.byref(pll), 1, None),
+        "biquad_create": (0, _lib.F32, ctypes.byref(bq), 48000.0, 1, None),
+    }
+    for name, args in creates.items():
+        assert getattr(L, "sdrgpu_" + name)(*args) == _lib.ERR_INVALID, name
+
+
 def test_no_device_error_on_cpu_box(sdr):
     from sdrgpu import _lib
     if sdr.device_count() > 0:

@@ -121,15 +121,7 @@ int sdrgpu_biquad_create(int device, int sample_kind, const sdrgpu_biquad_design
     int ident = 0;
     int st = bq_design(*d, rate, c, &ident);
     if (st) return st;
-    auto* h = new (std::nothrow) sdrgpu_biquad();
-    if (!h) return SDRGPU_ERR_NOMEM;
-    if ((st = h->init(device, sample_kind, c, ident, nch))) {
-        h->free_all();
-        delete h;
-        return st;
-    }
-    *out = h;
-    return SDRGPU_OK;
+    return make_handle(out, [&](sdrgpu_biquad* h) { return h->init(device, sample_kind, c, ident, nch); });
 }
 
 int sdrgpu_biquad_coefs(const sdrgpu_biquad* h, float* coefs5) {
@@ -139,16 +131,11 @@ int sdrgpu_biquad_coefs(const sdrgpu_biquad* h, float* coefs5) {
 }
 
 int sdrgpu_biquad_set_stream(sdrgpu_biquad* h, void* s) {
-    if (!h) return SDRGPU_ERR_INVALID;
-    DeviceGuard g(h->device);
-    if (!g.ok()) return SDRGPU_ERR_DEVICE;
-    return h->stream.set(s);
+    return h ? set_stream(h->device, h->stream, s) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_biquad_get_stream(const sdrgpu_biquad* h, void** s) {
-    if (!h || !s) return SDRGPU_ERR_INVALID;
-    *s = h->stream.cur;
-    return SDRGPU_OK;
+    return h ? get_stream(h->stream, s) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_biquad_process(sdrgpu_biquad* h, const void* in, size_t ld_in, size_t n, void* out,
@@ -199,10 +186,7 @@ int sdrgpu_biquad_last_time_parallel(sdrgpu_biquad* h, long* segments, long* rec
 }
 
 int sdrgpu_biquad_sync(sdrgpu_biquad* h) {
-    if (!h) return SDRGPU_ERR_INVALID;
-    DeviceGuard g(h->device);
-    SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
-    return SDRGPU_OK;
+    return h ? sync_stream(h->device, h->stream) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_biquad_reset(sdrgpu_biquad* h) {
@@ -211,33 +195,20 @@ int sdrgpu_biquad_reset(sdrgpu_biquad* h) {
 }
 
 int sdrgpu_biquad_clone(const sdrgpu_biquad* h, sdrgpu_biquad** out) {
-    if (!h || !out) return SDRGPU_ERR_INVALID;
-    *out = nullptr;
-    auto* c = new (std::nothrow) sdrgpu_biquad();
-    if (!c) return SDRGPU_ERR_NOMEM;
-    int st = c->init(h->device, h->sk, h->c, h->ident, h->nch);
-    c->tp.want_seg = h->tp.want_seg;
-    c->tp.want_warm = h->tp.want_warm;
-    if (!st) {
+    if (!h) return SDRGPU_ERR_INVALID;
+    return make_handle(out, [&](sdrgpu_biquad* c) -> int {
+        if (int st = c->init(h->device, h->sk, h->c, h->ident, h->nch)) return st;
+        c->tp.want_seg = h->tp.want_seg;
+        c->tp.want_warm = h->tp.want_warm;
         DeviceGuard g(h->device);
         if (hipMemcpyAsync(c->d_state, h->d_state, h->nch * sizeof(BiquadState),
                            hipMemcpyDeviceToDevice, h->stream.cur) != hipSuccess ||
             hipStreamSynchronize(h->stream.cur) != hipSuccess)
-            st = SDRGPU_ERR_DEVICE;
-    }
-    if (st) {
-        c->free_all();
-        delete c;
-        return st;
-    }
-    *out = c;
-    return SDRGPU_OK;
+            return SDRGPU_ERR_DEVICE;
+        return SDRGPU_OK;
+    });
 }
 
-void sdrgpu_biquad_destroy(sdrgpu_biquad* h) {
-    if (!h) return;
-    h->free_all();
-    delete h;
-}
+void sdrgpu_biquad_destroy(sdrgpu_biquad* h) { destroy_handle(h); }
 
 }  // extern "C"

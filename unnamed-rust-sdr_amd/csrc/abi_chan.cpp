@@ -9,12 +9,9 @@
 // (chan.hip computes every frame with the same arithmetic wherever it falls).  A channel count
 // that is not a power of two (sdrgpu_chan_create_any) runs chan_gen.hip's kernel with the tile
 // plan and the W_M table made here at create; everything else of the handle is the same.
-#include <new>
 #include <vector>
 
-#include "abi_common.hpp"
-#include "chan_kernels.hpp"
-#include "fft_tile.hpp"
+#include "abi_bank.hpp"
 
 using namespace sdrgpu;
 using namespace sdrgpu::detail;
@@ -23,51 +20,16 @@ using namespace sdrgpu::detail;
 // c64 at 4096 channels) and every frame reads P*nch samples
 static constexpr size_t kChanMaxP = 64;
 
-struct sdrgpu_chan {
-    int device = 0;
+// BankCore (abi_bank.hpp): d_taps is polyphase-major (chan_kernels.hpp: taps_pm), the history
+// P*M - 1 samples
+struct sdrgpu_chan : BankCore {
     int sk = SDRGPU_C64;
-    int M = 2, P = 1;
-    int os = 1;                            // oversampling factor; frames are D = M / os apart
-    bool general = false;                  // M is not a power of two: chan_gen.hip, `gen`, d_tw = W_M
-    ChanGenPlan gen;
-    std::vector<float> taps;               // as given (clone)
-    float* d_taps_pm = nullptr;            // P*M, polyphase-major (chan_kernels.hpp)
-    float2* d_tw = nullptr;
-    float2* d_hist[2] = {nullptr, nullptr};  // ping-pong, P*M - 1 samples each
-    int cur = 0;
+    ChanGenPlan gen;                       // general
     unsigned long long seen = 0;           // stream samples consumed
-    StreamSlot stream;
-    DevBuf stage_in, stage_out, stage_alias;
 
     size_t in_bytes() const { return kind_bytes(sk); }
     size_t H() const { return (size_t)P * M - 1; }
-    unsigned D() const { return (unsigned)(M / os); }
     size_t out_len(size_t n_in) const { return (size_t)((seen % D() + n_in) / D()); }
-
-    void free_all() {
-        DeviceGuard g(device);
-        if (d_taps_pm) (void)hipFree(d_taps_pm);
-        if (d_tw) (void)hipFree(d_tw);
-        for (auto& p : d_hist)
-            if (p) (void)hipFree(p);
-        d_taps_pm = nullptr;
-        d_tw = nullptr;
-        d_hist[0] = d_hist[1] = nullptr;
-        stage_in.release();
-        stage_out.release();
-        stage_alias.release();
-        stream.destroy();
-    }
-
-    int reset_state() {
-        DeviceGuard g(device);
-        if (!g.ok()) return SDRGPU_ERR_DEVICE;
-        seen = 0;
-        cur = 0;
-        SDRGPU_HIP_TRY(hipMemsetAsync(d_hist[0], 0, H() * sizeof(float2), stream.cur));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        return SDRGPU_OK;
-    }
 
     // any_m: take every channel count chan_gen_plan has a tile for, not only the powers of two
     int init(int dev, int sample_kind, const float* h, size_t ntaps, size_t nch, uint32_t oversample,
@@ -77,31 +39,14 @@ struct sdrgpu_chan {
             return sample_kind == SDRGPU_F32 ? SDRGPU_ERR_UNSUPPORTED : SDRGPU_ERR_INVALID;
         general = !chan_size_ok(nch);
         if (general && !(any_m && chan_gen_plan(nch, gen))) return SDRGPU_ERR_UNSUPPORTED;
-        if ((ntaps + nch - 1) / nch > kChanMaxP) return SDRGPU_ERR_UNSUPPORTED;
+        const size_t p = (ntaps + nch - 1) / nch;
+        if (p > kChanMaxP) return SDRGPU_ERR_UNSUPPORTED;
         if (!chan_os_ok(nch, oversample)) return SDRGPU_ERR_UNSUPPORTED;
-        int st = check_device(dev);
-        if (st) return st;
-        device = dev;
         sk = sample_kind;
-        M = (int)nch;
-        os = (int)oversample;
-        P = (int)((ntaps + nch - 1) / nch);
-        taps.assign(h, h + ntaps);
-
-        DeviceGuard g(device);
-        if (!g.ok()) return SDRGPU_ERR_DEVICE;
-        if ((st = stream.create())) return st;
         // taps_pm[q*M + r] = h[q*M + M-1-r]: lane r of a wave reads consecutive floats
-        std::vector<float> pm((size_t)P * M, 0.0f);
-        for (size_t n = 0; n < ntaps; ++n) pm[n / M * M + (M - 1 - n % M)] = h[n];
-        const std::vector<float2> tw = general ? twiddles(M) : fftd::tile_twiddles();
-        SDRGPU_HIP_TRY(hipMalloc(&d_taps_pm, pm.size() * sizeof(float)));
-        SDRGPU_HIP_TRY(hipMemcpy(d_taps_pm, pm.data(), pm.size() * sizeof(float), hipMemcpyHostToDevice));
-        SDRGPU_HIP_TRY(hipMalloc(&d_tw, tw.size() * sizeof(float2)));
-        SDRGPU_HIP_TRY(hipMemcpy(d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
-        SDRGPU_HIP_TRY(hipMalloc(&d_hist[0], H() * sizeof(float2)));
-        SDRGPU_HIP_TRY(hipMalloc(&d_hist[1], H() * sizeof(float2)));
-        return reset_state();
+        std::vector<float> pm(p * nch, 0.0f);
+        for (size_t n = 0; n < ntaps; ++n) pm[n / nch * nch + (nch - 1 - n % nch)] = h[n];
+        return setup(dev, h, ntaps, nch, oversample, pm, (p * nch - 1) * sizeof(float2), seen);
     }
 
     // Enqueue one block (device pointers) on the current stream; ld_out >= out_len(n_in).
@@ -123,7 +68,7 @@ struct sdrgpu_chan {
         a.rot0 = (int)((seen / D() + 1) % (unsigned)os);
         a.nframes = (long)n_out;
         a.P = P;
-        a.taps_pm = d_taps_pm;
+        a.taps_pm = d_taps;
         a.tw = d_tw;
         a.out = static_cast<float2*>(d_out);
         a.ld_out = (long)ld_out;
@@ -156,34 +101,10 @@ struct sdrgpu_chan {
     int clone_into(sdrgpu_chan* dst) const {
         int st = dst->init(device, sk, taps.data(), taps.size(), (size_t)M, (uint32_t)os, general);
         if (st) return st;
-        DeviceGuard g(device);
         dst->seen = seen;
-        SDRGPU_HIP_TRY(hipMemcpyAsync(dst->d_hist[0], d_hist[cur], H() * sizeof(float2),
-                                      hipMemcpyDeviceToDevice, stream.cur));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        return SDRGPU_OK;
+        return copy_history_to(*dst);
     }
 };
-
-namespace {
-
-template <class Init>
-int make_handle(sdrgpu_chan** out, Init init) {
-    if (!out) return SDRGPU_ERR_INVALID;
-    *out = nullptr;
-    auto* h = new (std::nothrow) sdrgpu_chan();
-    if (!h) return SDRGPU_ERR_NOMEM;
-    const int st = init(h);
-    if (st) {
-        h->free_all();
-        delete h;
-        return st;
-    }
-    *out = h;
-    return SDRGPU_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -217,23 +138,14 @@ int sdrgpu_chan_clone(const sdrgpu_chan* h, sdrgpu_chan** out) {
     return make_handle(out, [&](sdrgpu_chan* c) { return h->clone_into(c); });
 }
 
-void sdrgpu_chan_destroy(sdrgpu_chan* h) {
-    if (!h) return;
-    h->free_all();
-    delete h;
-}
+void sdrgpu_chan_destroy(sdrgpu_chan* h) { destroy_handle(h); }
 
 int sdrgpu_chan_set_stream(sdrgpu_chan* h, void* s) {
-    if (!h) return SDRGPU_ERR_INVALID;
-    DeviceGuard g(h->device);
-    if (!g.ok()) return SDRGPU_ERR_DEVICE;
-    return h->stream.set(s);
+    return h ? set_stream(h->device, h->stream, s) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_chan_get_stream(const sdrgpu_chan* h, void** s) {
-    if (!h || !s) return SDRGPU_ERR_INVALID;
-    *s = h->stream.cur;
-    return SDRGPU_OK;
+    return h ? get_stream(h->stream, s) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_chan_output_len(const sdrgpu_chan* h, size_t n_in, size_t* n_out) {
@@ -262,13 +174,8 @@ int sdrgpu_chan_process_dev(sdrgpu_chan* h, const void* d_in, size_t n_in, void*
     return h->run_dev(d_in, n_in, d_out, ld_out);
 }
 
-int sdrgpu_chan_sync(sdrgpu_chan* h) {
-    if (!h) return SDRGPU_ERR_INVALID;
-    DeviceGuard g(h->device);
-    SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
-    return SDRGPU_OK;
-}
+int sdrgpu_chan_sync(sdrgpu_chan* h) { return h ? sync_stream(h->device, h->stream) : SDRGPU_ERR_INVALID; }
 
-int sdrgpu_chan_reset(sdrgpu_chan* h) { return h ? h->reset_state() : SDRGPU_ERR_INVALID; }
+int sdrgpu_chan_reset(sdrgpu_chan* h) { return h ? h->reset(h->seen) : SDRGPU_ERR_INVALID; }
 
 }  // extern "C"

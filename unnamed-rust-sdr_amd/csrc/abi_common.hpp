@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <new>
 #include <utility>
 
 #include "common.hpp"
@@ -85,6 +86,45 @@ struct StreamSlot {
     }
 };
 
+// Handle lifecycle of the families that return sdrgpu error codes (fir, firbank, chan, synth, fft,
+// stft, pll, biquad; the extern "C" functions check the handle for NULL).  A handle H has
+// free_all(), which releases whatever a failed or finished init left.
+// out == NULL: INVALID.  *out: the new handle once init(handle) has returned 0, else NULL.
+template <class H, class Init>
+int make_handle(H** out, Init init) {
+    if (!out) return SDRGPU_ERR_INVALID;
+    *out = nullptr;
+    auto* h = new (std::nothrow) H();
+    if (!h) return SDRGPU_ERR_NOMEM;
+    const int st = init(h);
+    if (st) {
+        h->free_all();
+        delete h;
+        return st;
+    }
+    *out = h;
+    return SDRGPU_OK;
+}
+
+template <class H>
+void destroy_handle(H* h) {
+    if (!h) return;
+    h->free_all();
+    delete h;
+}
+
+inline int set_stream(int device, StreamSlot& slot, void* s) {
+    DeviceGuard g(device);
+    if (!g.ok()) return SDRGPU_ERR_DEVICE;
+    return slot.set(s);
+}
+
+inline int get_stream(const StreamSlot& slot, void** s) {
+    if (!s) return SDRGPU_ERR_INVALID;
+    *s = slot.cur;
+    return SDRGPU_OK;
+}
+
 // Asynchronous host streaming (the Block adapter's producer/consumer split,
 // src/signal/adapters/block.rs:105-207, with the GPU as the consumer): a block's H2D and
 // kernel go on the handle's stream, its download on a second stream, so block i's D2H
@@ -161,6 +201,13 @@ struct AsyncD2H {
         d2h = nullptr;
     }
 };
+
+// Waits for the handle's stream, and for the downloads of its async calls where it has them.
+inline int sync_stream(int device, const StreamSlot& slot, AsyncD2H* async = nullptr) {
+    DeviceGuard g(device);
+    SDRGPU_HIP_TRY(hipStreamSynchronize(slot.cur));
+    return async ? async->sync() : SDRGPU_OK;
+}
 
 // A handle's time-parallel blocks (time_parallel.hpp; the PLL and the biquad): what the caller
 // asked for, the part of the plan both share, the scratch, the record of the most recent block.

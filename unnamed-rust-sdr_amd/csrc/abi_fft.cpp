@@ -70,6 +70,13 @@ struct sdrgpu_stft {
         return (size_t)((seen + n_in) / h - seen / h);
     }
     long first_end() const { return hop - (long)(seen % (unsigned long long)hop); }
+    void free_all() {
+        DeviceGuard g(fft.device);
+        for (auto& p : d_hist)
+            if (p) (void)hipFree(p);
+        d_hist[0] = d_hist[1] = nullptr;
+        fft.free_all();
+    }
 };
 
 extern "C" {
@@ -79,29 +86,15 @@ int sdrgpu_fft_plan(int device, size_t n, sdrgpu_fft** out) {
     *out = nullptr;
     if (n == 0) return SDRGPU_ERR_INVALID;
     if (n > (1u << 24)) return SDRGPU_ERR_UNSUPPORTED;
-    auto* h = new (std::nothrow) sdrgpu_fft();
-    if (!h) return SDRGPU_ERR_NOMEM;
-    int st = fft_init(h, device, n);
-    if (st) {
-        h->free_all();
-        delete h;
-        return st;
-    }
-    *out = h;
-    return SDRGPU_OK;
+    return make_handle(out, [&](sdrgpu_fft* h) { return fft_init(h, device, n); });
 }
 
 int sdrgpu_fft_set_stream(sdrgpu_fft* h, void* s) {
-    if (!h) return SDRGPU_ERR_INVALID;
-    DeviceGuard g(h->device);
-    if (!g.ok()) return SDRGPU_ERR_DEVICE;
-    return h->stream.set(s);
+    return h ? set_stream(h->device, h->stream, s) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_fft_get_stream(const sdrgpu_fft* h, void** s) {
-    if (!h || !s) return SDRGPU_ERR_INVALID;
-    *s = h->stream.cur;
-    return SDRGPU_OK;
+    return h ? get_stream(h->stream, s) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_fft_exec_dev(sdrgpu_fft* h, const void* d_in, void* d_out, size_t count) {
@@ -179,17 +172,10 @@ int sdrgpu_fft_set_output(sdrgpu_fft* h, int mode) {
 }
 
 int sdrgpu_fft_sync(sdrgpu_fft* h) {
-    if (!h) return SDRGPU_ERR_INVALID;
-    DeviceGuard g(h->device);
-    SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
-    return h->async.sync();
+    return h ? sync_stream(h->device, h->stream, &h->async) : SDRGPU_ERR_INVALID;
 }
 
-void sdrgpu_fft_destroy(sdrgpu_fft* h) {
-    if (!h) return;
-    h->free_all();
-    delete h;
-}
+void sdrgpu_fft_destroy(sdrgpu_fft* h) { destroy_handle(h); }
 
 // fft.rs:18,24: freq = (i - n/2) as f32 * (rate / n as f32)
 int sdrgpu_fft_freqs(size_t n, float rate, float* freqs) {
@@ -206,38 +192,24 @@ int sdrgpu_stft_create(int device, size_t n, size_t hop, sdrgpu_stft** out) {
     *out = nullptr;
     if (n == 0 || hop == 0) return SDRGPU_ERR_INVALID;
     if (n > (1u << 24)) return SDRGPU_ERR_UNSUPPORTED;
-    auto* h = new (std::nothrow) sdrgpu_stft();
-    if (!h) return SDRGPU_ERR_NOMEM;
-    int st = fft_init(&h->fft, device, n);
-    if (!st) {
+    return make_handle(out, [&](sdrgpu_stft* h) -> int {
+        if (int st = fft_init(&h->fft, device, n)) return st;
         h->hop = (long)hop;
         h->H = (long)n - 1;
         DeviceGuard g(device);
         if (hipMalloc(&h->d_hist[0], h->H * sizeof(float2)) != hipSuccess ||
             hipMalloc(&h->d_hist[1], h->H * sizeof(float2)) != hipSuccess)
-            st = SDRGPU_ERR_NOMEM;
-        else
-            st = sdrgpu_stft_reset(h);
-    }
-    if (st) {
-        sdrgpu_stft_destroy(h);
-        return st;
-    }
-    *out = h;
-    return SDRGPU_OK;
+            return SDRGPU_ERR_NOMEM;
+        return sdrgpu_stft_reset(h);
+    });
 }
 
 int sdrgpu_stft_set_stream(sdrgpu_stft* h, void* s) {
-    if (!h) return SDRGPU_ERR_INVALID;
-    DeviceGuard g(h->fft.device);
-    if (!g.ok()) return SDRGPU_ERR_DEVICE;
-    return h->fft.stream.set(s);
+    return h ? set_stream(h->fft.device, h->fft.stream, s) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_stft_get_stream(const sdrgpu_stft* h, void** s) {
-    if (!h || !s) return SDRGPU_ERR_INVALID;
-    *s = h->fft.stream.cur;
-    return SDRGPU_OK;
+    return h ? get_stream(h->fft.stream, s) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_stft_output_len(const sdrgpu_stft* h, size_t n_in, size_t* n_frames) {
@@ -339,13 +311,7 @@ int sdrgpu_stft_set_output(sdrgpu_stft* h, int mode) {
     return sdrgpu_fft_set_output(&h->fft, mode);
 }
 
-int sdrgpu_stft_sync(sdrgpu_stft* h) {
-    if (!h) return SDRGPU_ERR_INVALID;
-    int st = sdrgpu_fft_sync(&h->fft);
-    if (st) return st;
-    DeviceGuard g(h->fft.device);
-    return h->fft.async.sync();
-}
+int sdrgpu_stft_sync(sdrgpu_stft* h) { return h ? sdrgpu_fft_sync(&h->fft) : SDRGPU_ERR_INVALID; }
 
 int sdrgpu_stft_reset(sdrgpu_stft* h) {
     if (!h) return SDRGPU_ERR_INVALID;
@@ -359,15 +325,6 @@ int sdrgpu_stft_reset(sdrgpu_stft* h) {
     return SDRGPU_OK;
 }
 
-void sdrgpu_stft_destroy(sdrgpu_stft* h) {
-    if (!h) return;
-    {
-        DeviceGuard g(h->fft.device);
-        for (auto& p : h->d_hist)
-            if (p) (void)hipFree(p);
-    }
-    h->fft.free_all();
-    delete h;
-}
+void sdrgpu_stft_destroy(sdrgpu_stft* h) { destroy_handle(h); }
 
 }  // extern "C"

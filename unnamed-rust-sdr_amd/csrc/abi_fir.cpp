@@ -5,7 +5,6 @@
 // (src/signal/adapters/mod.rs:19-37).  Stream state (K-1 history per channel, decimation
 // phase) is carried across calls so block partitioning never changes the outputs.  Which kernel
 // filters a block is FirPaths' business (fir_select.cpp).
-#include <new>
 #include <vector>
 
 #include "fir_select.hpp"
@@ -57,17 +56,6 @@ struct FirCore {
         paths.release();
         async.release();
         stream.destroy();
-    }
-    int sync_stream() {
-        DeviceGuard g(device);
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        return SDRGPU_OK;
-    }
-    int sync_all() {
-        const int st = sync_stream();
-        if (st) return st;
-        DeviceGuard g(device);
-        return async.sync();
     }
 
     int reset_state() {
@@ -228,22 +216,6 @@ struct sdrgpu_firbank : FirCore {};
 
 namespace {
 
-template <class H, class Init>
-int make_handle(H** out, Init init) {
-    if (!out) return SDRGPU_ERR_INVALID;
-    *out = nullptr;
-    auto* h = new (std::nothrow) H();
-    if (!h) return SDRGPU_ERR_NOMEM;
-    const int st = init(h);
-    if (st) {
-        h->free_all();
-        delete h;
-        return st;
-    }
-    *out = h;
-    return SDRGPU_OK;
-}
-
 template <class H>
 int create(H** out, int device, int sample_kind, int tap_kind, const void* taps, size_t ntaps,
            uint32_t decim, size_t nch) {
@@ -258,29 +230,15 @@ int clone(const H* h, H** out) {
     return make_handle(out, [&](FirCore* c) { return h->clone_into(c); });
 }
 
-template <class H>
-void destroy(H* h) {
-    if (!h) return;
-    h->free_all();
-    delete h;
-}
-
 int set_algorithm(FirCore* c, int algo) {
     return c ? c->paths.set_algorithm(algo) : SDRGPU_ERR_INVALID;
 }
 
 int set_stream(FirCore* c, void* s) {
-    if (!c) return SDRGPU_ERR_INVALID;
-    DeviceGuard g(c->device);
-    if (!g.ok()) return SDRGPU_ERR_DEVICE;
-    return c->stream.set(s);
+    return c ? detail::set_stream(c->device, c->stream, s) : SDRGPU_ERR_INVALID;
 }
 
-int get_stream(const FirCore* c, void** s) {
-    if (!c || !s) return SDRGPU_ERR_INVALID;
-    *s = c->stream.cur;
-    return SDRGPU_OK;
-}
+int get_stream(const FirCore* c, void** s) { return c ? detail::get_stream(c->stream, s) : SDRGPU_ERR_INVALID; }
 
 int output_len(const FirCore* c, size_t n_in, size_t* n_out) {
     if (!c || !n_out) return SDRGPU_ERR_INVALID;
@@ -313,8 +271,8 @@ int sdrgpu_firbank_create(int device, int sample_kind, int tap_kind, const void*
 int sdrgpu_fir_clone(const sdrgpu_fir* h, sdrgpu_fir** out) { return clone(h, out); }
 int sdrgpu_firbank_clone(const sdrgpu_firbank* h, sdrgpu_firbank** out) { return clone(h, out); }
 
-void sdrgpu_fir_destroy(sdrgpu_fir* h) { destroy(h); }
-void sdrgpu_firbank_destroy(sdrgpu_firbank* h) { destroy(h); }
+void sdrgpu_fir_destroy(sdrgpu_fir* h) { destroy_handle(h); }
+void sdrgpu_firbank_destroy(sdrgpu_firbank* h) { destroy_handle(h); }
 
 int sdrgpu_fir_set_algorithm(sdrgpu_fir* h, int algo) { return set_algorithm(h, algo); }
 int sdrgpu_firbank_set_algorithm(sdrgpu_firbank* h, int algo) { return set_algorithm(h, algo); }
@@ -373,7 +331,9 @@ int sdrgpu_fir_process_dev(sdrgpu_fir* h, const void* d_in, size_t n_in, void* d
     return h->run_dev(d_in, n_in, n_in, d_out, out_cap, n_out);
 }
 
-int sdrgpu_fir_sync(sdrgpu_fir* h) { return h ? h->sync_all() : SDRGPU_ERR_INVALID; }
+int sdrgpu_fir_sync(sdrgpu_fir* h) {
+    return h ? sync_stream(h->device, h->stream, &h->async) : SDRGPU_ERR_INVALID;
+}
 
 // ------------------------------- FIR bank ------------------------------------------
 int sdrgpu_firbank_process(sdrgpu_firbank* h, const void* in, size_t ld_in, size_t n_in,
@@ -396,6 +356,8 @@ int sdrgpu_firbank_process_dev(sdrgpu_firbank* h, const void* d_in, size_t ld_in
 }
 
 // the bank has no async call: only the compute stream can hold its work
-int sdrgpu_firbank_sync(sdrgpu_firbank* h) { return h ? h->sync_stream() : SDRGPU_ERR_INVALID; }
+int sdrgpu_firbank_sync(sdrgpu_firbank* h) {
+    return h ? sync_stream(h->device, h->stream) : SDRGPU_ERR_INVALID;
+}
 
 }  // extern "C"

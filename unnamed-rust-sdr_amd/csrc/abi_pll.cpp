@@ -151,6 +151,30 @@ struct sdrgpu_pll {
         tp.buf.release();
         stream.destroy();
     }
+
+    // p, nch and dev have passed sdrgpu_pll_create's checks
+    int init(int dev, const sdrgpu_pll_params& p, size_t nch) {
+        device = dev;
+        params = p;
+        dp.nch = (long)nch;
+        dp.rate = p.rate;
+        dp.reference = p.reference / p.rate;  // pll.rs:51
+        dp.gain = p.gain;
+        int st;
+        if ((st = bq_design(p.loopf, p.rate, dp.loopc, &dp.loop_ident)) ||
+            (st = bq_design(p.outputf, p.rate, dp.outc, &dp.out_ident)) ||
+            (st = bq_design(p.lockf, p.rate, dp.lockc, &dp.lock_ident)))
+            return st;
+        DeviceGuard g(device);
+        if (!g.ok()) return SDRGPU_ERR_DEVICE;
+        if ((st = stream.create())) return st;
+        if (hipMalloc(&d_state, nch * sizeof(PllChannelState)) != hipSuccess) return SDRGPU_ERR_NOMEM;
+        if (hipHostMalloc(reinterpret_cast<void**>(&probe_host), sizeof(*probe_host)) != hipSuccess ||
+            hipEventCreateWithFlags(&probe_ev, hipEventDisableTiming) != hipSuccess)
+            return SDRGPU_ERR_NOMEM;
+        tp.init(device);
+        return sdrgpu_pll_reset(this);
+    }
 };
 
 extern "C" {
@@ -170,41 +194,8 @@ int sdrgpu_pll_create(int device, const sdrgpu_pll_params* p, size_t nch, sdrgpu
     if (!out) return SDRGPU_ERR_INVALID;
     *out = nullptr;
     if (!p || nch == 0 || !(p->rate > 0.0f)) return SDRGPU_ERR_INVALID;
-    int st = check_device(device);
-    if (st) return st;
-    auto* h = new (std::nothrow) sdrgpu_pll();
-    if (!h) return SDRGPU_ERR_NOMEM;
-    h->device = device;
-    h->params = *p;
-    PllDevParams& d = h->dp;
-    d.nch = (long)nch;
-    d.rate = p->rate;
-    d.reference = p->reference / p->rate;  // pll.rs:51
-    d.gain = p->gain;
-    if ((st = bq_design(p->loopf, p->rate, d.loopc, &d.loop_ident)) ||
-        (st = bq_design(p->outputf, p->rate, d.outc, &d.out_ident)) ||
-        (st = bq_design(p->lockf, p->rate, d.lockc, &d.lock_ident))) {
-        delete h;
-        return st;
-    }
-    {
-        DeviceGuard g(device);
-        if (!g.ok()) st = SDRGPU_ERR_DEVICE;
-        if (!st) st = h->stream.create();
-        if (!st && hipMalloc(&h->d_state, nch * sizeof(PllChannelState)) != hipSuccess) st = SDRGPU_ERR_NOMEM;
-        if (!st && (hipHostMalloc(reinterpret_cast<void**>(&h->probe_host), sizeof(*h->probe_host)) != hipSuccess ||
-                    hipEventCreateWithFlags(&h->probe_ev, hipEventDisableTiming) != hipSuccess))
-            st = SDRGPU_ERR_NOMEM;
-        if (!st) h->tp.init(device);
-    }
-    if (!st) st = sdrgpu_pll_reset(h);
-    if (st) {
-        h->free_all();
-        delete h;
-        return st;
-    }
-    *out = h;
-    return SDRGPU_OK;
+    if (int st = check_device(device)) return st;
+    return make_handle(out, [&](sdrgpu_pll* h) { return h->init(device, *p, nch); });
 }
 
 int sdrgpu_pll_set_input_kind(sdrgpu_pll* h, int sample_kind) {
@@ -261,16 +252,11 @@ int sdrgpu_pll_last_phase_ms(sdrgpu_pll* h, float* pass1, float* rerun, float* w
 }
 
 int sdrgpu_pll_set_stream(sdrgpu_pll* h, void* s) {
-    if (!h) return SDRGPU_ERR_INVALID;
-    DeviceGuard g(h->device);
-    if (!g.ok()) return SDRGPU_ERR_DEVICE;
-    return h->stream.set(s);
+    return h ? set_stream(h->device, h->stream, s) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_pll_get_stream(const sdrgpu_pll* h, void** s) {
-    if (!h || !s) return SDRGPU_ERR_INVALID;
-    *s = h->stream.cur;
-    return SDRGPU_OK;
+    return h ? get_stream(h->stream, s) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_pll_process_dev(sdrgpu_pll* h, const void* d_in, size_t ld_in, size_t n, float* d_out,
@@ -363,25 +349,25 @@ int sdrgpu_pll_state(sdrgpu_pll* h, size_t ch, float* nphase, float* value_re_im
 }
 
 int sdrgpu_pll_sync(sdrgpu_pll* h) {
-    if (!h) return SDRGPU_ERR_INVALID;
-    DeviceGuard g(h->device);
-    SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
-    return h->async.sync();
+    return h ? sync_stream(h->device, h->stream, &h->async) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_pll_clone(const sdrgpu_pll* h, sdrgpu_pll** out) {
-    if (!h || !out) return SDRGPU_ERR_INVALID;
-    int st = sdrgpu_pll_create(h->device, &h->params, (size_t)h->dp.nch, out);
-    if (st) return st;
-    (*out)->dp.out_mode = h->dp.out_mode;
-    (*out)->dp.in_u8 = h->dp.in_u8;
-    (*out)->tp.want_seg = h->tp.want_seg;
-    (*out)->tp.want_warm = h->tp.want_warm;
-    DeviceGuard g(h->device);
-    SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
-    SDRGPU_HIP_TRY(hipMemcpy((*out)->d_state, h->d_state, h->dp.nch * sizeof(PllChannelState),
-                             hipMemcpyDeviceToDevice));
-    return SDRGPU_OK;
+    if (!h) return SDRGPU_ERR_INVALID;
+    return make_handle(out, [&](sdrgpu_pll* c) -> int {
+        int st = check_device(h->device);
+        if (!st) st = c->init(h->device, h->params, (size_t)h->dp.nch);
+        if (st) return st;
+        c->dp.out_mode = h->dp.out_mode;
+        c->dp.in_u8 = h->dp.in_u8;
+        c->tp.want_seg = h->tp.want_seg;
+        c->tp.want_warm = h->tp.want_warm;
+        DeviceGuard g(h->device);
+        SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
+        SDRGPU_HIP_TRY(hipMemcpy(c->d_state, h->d_state, h->dp.nch * sizeof(PllChannelState),
+                                 hipMemcpyDeviceToDevice));
+        return SDRGPU_OK;
+    });
 }
 
 int sdrgpu_debug_libm(int device, int fn, const float* a, const float* b, float* out0,
@@ -415,10 +401,6 @@ int sdrgpu_debug_libm(int device, int fn, const float* a, const float* b, float*
     return st;
 }
 
-void sdrgpu_pll_destroy(sdrgpu_pll* h) {
-    if (!h) return;
-    h->free_all();
-    delete h;
-}
+void sdrgpu_pll_destroy(sdrgpu_pll* h) { destroy_handle(h); }
 
 }  // extern "C"

@@ -7,12 +7,9 @@
 // (sdrgpu_synth_create_any) runs chan_syn_gen.hip on the mixed-radix tile engine, with the tile
 // plan and the W_M table made here at create; everything else of the handle is the same.
 #include <algorithm>
-#include <new>
 #include <vector>
 
-#include "abi_common.hpp"
-#include "chan_kernels.hpp"
-#include "fft_tile.hpp"
+#include "abi_bank.hpp"
 
 using namespace sdrgpu;
 using namespace sdrgpu::detail;
@@ -20,50 +17,13 @@ using namespace sdrgpu::detail;
 // frames that reach one output sample at most, as ceil(ntaps / D): the history is M*(Q - 1) frames
 static constexpr size_t kSynthMaxReach = 64;
 
-struct sdrgpu_synth {
-    int device = 0;
-    int M = 2, P = 1;
-    int os = 1;                              // oversampling factor; a frame is D = M / os samples
-    bool general = false;                    // M is not a power of two: chan_syn_gen.hip, `gen`, d_tw = W_M
-    SynthGenPlan gen;
-    std::vector<float> taps;                 // as given (clone)
-    float* d_taps = nullptr;                 // P*M, zero past the last tap
-    float2* d_tw = nullptr;
-    float2* d_hist[2] = {nullptr, nullptr};  // ping-pong, M*(Q - 1) frames each
-    int cur = 0;
+// BankCore (abi_bank.hpp): d_taps is the prototype, zero past the last tap, the history the last
+// Q - 1 frames of every row
+struct sdrgpu_synth : BankCore {
+    SynthGenPlan gen;                        // general
     unsigned long long frames = 0;           // frames consumed per channel
-    StreamSlot stream;
-    DevBuf stage_in, stage_out, stage_alias;
 
-    unsigned D() const { return (unsigned)(M / os); }
     size_t Q() const { return (size_t)P * os; }
-    size_t hist_len() const { return (size_t)M * (Q() - 1); }
-    size_t hist_bytes() const { return (hist_len() ? hist_len() : 1) * sizeof(float2); }
-
-    void free_all() {
-        DeviceGuard g(device);
-        if (d_taps) (void)hipFree(d_taps);
-        if (d_tw) (void)hipFree(d_tw);
-        for (auto& p : d_hist)
-            if (p) (void)hipFree(p);
-        d_taps = nullptr;
-        d_tw = nullptr;
-        d_hist[0] = d_hist[1] = nullptr;
-        stage_in.release();
-        stage_out.release();
-        stage_alias.release();
-        stream.destroy();
-    }
-
-    int reset_state() {
-        DeviceGuard g(device);
-        if (!g.ok()) return SDRGPU_ERR_DEVICE;
-        frames = 0;
-        cur = 0;
-        SDRGPU_HIP_TRY(hipMemsetAsync(d_hist[0], 0, hist_bytes(), stream.cur));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        return SDRGPU_OK;
-    }
 
     // any_m: take every channel count synth_gen_plan has a tile for, not only the powers of two
     int init(int dev, const float* g, size_t ntaps, size_t nch, uint32_t oversample, bool any_m) {
@@ -73,27 +33,11 @@ struct sdrgpu_synth {
         if (general && !(any_m && synth_gen_plan(nch, oversample, gen))) return SDRGPU_ERR_UNSUPPORTED;
         const size_t d = nch / oversample;
         if ((ntaps + d - 1) / d > kSynthMaxReach) return SDRGPU_ERR_UNSUPPORTED;
-        int st = check_device(dev);
-        if (st) return st;
-        device = dev;
-        M = (int)nch;
-        os = (int)oversample;
-        P = (int)((ntaps + nch - 1) / nch);
-        taps.assign(g, g + ntaps);
-
-        DeviceGuard guard(device);
-        if (!guard.ok()) return SDRGPU_ERR_DEVICE;
-        if ((st = stream.create())) return st;
-        std::vector<float> padded((size_t)P * M, 0.0f);
+        const size_t p = (ntaps + nch - 1) / nch;
+        std::vector<float> padded(p * nch, 0.0f);
         std::copy(g, g + ntaps, padded.begin());
-        const std::vector<float2> tw = general ? twiddles(M) : fftd::tile_twiddles();
-        SDRGPU_HIP_TRY(hipMalloc(&d_taps, padded.size() * sizeof(float)));
-        SDRGPU_HIP_TRY(hipMemcpy(d_taps, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice));
-        SDRGPU_HIP_TRY(hipMalloc(&d_tw, tw.size() * sizeof(float2)));
-        SDRGPU_HIP_TRY(hipMemcpy(d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
-        SDRGPU_HIP_TRY(hipMalloc(&d_hist[0], hist_bytes()));
-        SDRGPU_HIP_TRY(hipMalloc(&d_hist[1], hist_bytes()));
-        return reset_state();
+        const size_t hist_len = nch * (p * oversample - 1);
+        return setup(dev, g, ntaps, nch, oversample, padded, (hist_len ? hist_len : 1) * sizeof(float2), frames);
     }
 
     // Enqueue one block (device pointers) on the current stream; ld_in >= n, d_out holds n*D.
@@ -156,32 +100,12 @@ struct sdrgpu_synth {
     int clone_into(sdrgpu_synth* dst) const {
         int st = dst->init(device, taps.data(), taps.size(), (size_t)M, (uint32_t)os, general);
         if (st) return st;
-        DeviceGuard g(device);
         dst->frames = frames;
-        SDRGPU_HIP_TRY(hipMemcpyAsync(dst->d_hist[0], d_hist[cur], hist_bytes(), hipMemcpyDeviceToDevice,
-                                      stream.cur));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        return SDRGPU_OK;
+        return copy_history_to(*dst);
     }
 };
 
 namespace {
-
-template <class Init>
-int make_handle(sdrgpu_synth** out, Init init) {
-    if (!out) return SDRGPU_ERR_INVALID;
-    *out = nullptr;
-    auto* h = new (std::nothrow) sdrgpu_synth();
-    if (!h) return SDRGPU_ERR_NOMEM;
-    const int st = init(h);
-    if (st) {
-        h->free_all();
-        delete h;
-        return st;
-    }
-    *out = h;
-    return SDRGPU_OK;
-}
 
 // what both process calls check before anything is enqueued
 int check_block(const sdrgpu_synth* h, size_t ld_in, size_t n_frames, size_t out_cap, size_t* n_out) {
@@ -221,23 +145,14 @@ int sdrgpu_synth_clone(const sdrgpu_synth* h, sdrgpu_synth** out) {
     return make_handle(out, [&](sdrgpu_synth* c) { return h->clone_into(c); });
 }
 
-void sdrgpu_synth_destroy(sdrgpu_synth* h) {
-    if (!h) return;
-    h->free_all();
-    delete h;
-}
+void sdrgpu_synth_destroy(sdrgpu_synth* h) { destroy_handle(h); }
 
 int sdrgpu_synth_set_stream(sdrgpu_synth* h, void* s) {
-    if (!h) return SDRGPU_ERR_INVALID;
-    DeviceGuard g(h->device);
-    if (!g.ok()) return SDRGPU_ERR_DEVICE;
-    return h->stream.set(s);
+    return h ? set_stream(h->device, h->stream, s) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_synth_get_stream(const sdrgpu_synth* h, void** s) {
-    if (!h || !s) return SDRGPU_ERR_INVALID;
-    *s = h->stream.cur;
-    return SDRGPU_OK;
+    return h ? get_stream(h->stream, s) : SDRGPU_ERR_INVALID;
 }
 
 int sdrgpu_synth_output_len(const sdrgpu_synth* h, size_t n_frames, size_t* n_out) {
@@ -260,13 +175,8 @@ int sdrgpu_synth_process_dev(sdrgpu_synth* h, const void* d_in, size_t ld_in, si
     return h->run_dev(d_in, ld_in, n_frames, d_out);
 }
 
-int sdrgpu_synth_sync(sdrgpu_synth* h) {
-    if (!h) return SDRGPU_ERR_INVALID;
-    DeviceGuard g(h->device);
-    SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
-    return SDRGPU_OK;
-}
+int sdrgpu_synth_sync(sdrgpu_synth* h) { return h ? sync_stream(h->device, h->stream) : SDRGPU_ERR_INVALID; }
 
-int sdrgpu_synth_reset(sdrgpu_synth* h) { return h ? h->reset_state() : SDRGPU_ERR_INVALID; }
+int sdrgpu_synth_reset(sdrgpu_synth* h) { return h ? h->reset(h->frames) : SDRGPU_ERR_INVALID; }
 
 }  // extern "C"

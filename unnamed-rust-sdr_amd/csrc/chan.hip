@@ -94,13 +94,7 @@ __global__ __launch_bounds__(BLK) void chan_tile_kernel(ChanArgs a) {
     constexpr int D = M / OS;  // frame stride
     extern __shared__ float2 lds[];  // ChanTile::LDS
     const int t = threadIdx.x;
-    if (blockIdx.x >= a.ntiles) {
-        // history carry: hist_next[j] = stream sample n_in - H + j
-        const long nb = gridDim.x - a.ntiles;
-        for (long j = (long)(blockIdx.x - a.ntiles) * BLK + t; j < a.H; j += nb * BLK)
-            a.hist_next[j] = stream_sample<U8>(a, a.n_in - a.H + j);
-        return;
-    }
+    if (blockIdx.x >= a.ntiles) return chan_carry<U8, BLK>(a, t);
     const long f0 = (long)blockIdx.x * F;
     const int nf = (int)min((long)F, a.nframes - f0);
     const int npts = nf * M;
@@ -191,8 +185,8 @@ __global__ __launch_bounds__(BLK) void chan_tile_kernel(ChanArgs a) {
         if constexpr (OS == 1) {
             if (f < nf) a.out[(long)k * a.ld_out + f0 + f] = lds[f * PITCH + k];
         } else {
-            // baseband centring: rot(k, m) = (-j)^(4/OS k (m + 1)), m + 1 = a.rot0 + f0 + f mod OS
-            const int e = (k * (int)((a.rot0 + f0 + f) & (OS - 1)) & (OS - 1)) * (4 / OS);
+            // baseband centring by rot(k, m), m + 1 = a.rot0 + f0 + f mod OS
+            const int e = rot_exponent<OS>(k, (int)(a.rot0 + f0 + f));
             if (f < nf) a.out[(long)k * a.ld_out + f0 + f] = rot_quarter(lds[f * PITCH + k], e);
         }
     }
@@ -203,51 +197,17 @@ int launch_kind(ChanArgs a, hipStream_t s) {
     constexpr int BLK = M >= kChanBigMinM ? 1024 : kFftBlock;
     using Tile = ChanTile<M, BLK>;
     constexpr size_t lds = (size_t)Tile::LDS * sizeof(float2);
-    static const bool attr = hipFuncSetAttribute((const void*)chan_tile_kernel<M, OS, U8, BLK>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)lds) == hipSuccess;
-    if (!attr) return SDRGPU_ERR_LAUNCH;
     a.ntiles = (unsigned)ceil_div(a.nframes, (long)Tile::F);
-    const long ncarry = std::min<long>(ceil_div(a.H, (long)BLK), 128);
-    hipLaunchKernelGGL((chan_tile_kernel<M, OS, U8, BLK>), dim3(a.ntiles + (unsigned)ncarry), dim3(BLK),
-                       lds, s, a);
-    SDRGPU_LAUNCH_CHECK();
-    return SDRGPU_OK;
-}
-
-template <int M, int OS>
-int launch_os(int sample_kind, const ChanArgs& a, hipStream_t s) {
-    if constexpr (OS > M) return SDRGPU_ERR_INVALID;
-    else return sample_kind == SDRGPU_CU8 ? launch_kind<M, OS, true>(a, s) : launch_kind<M, OS, false>(a, s);
-}
-
-template <int M>
-int launch_m(int sample_kind, const ChanArgs& a, hipStream_t s) {
-    switch (a.os) {
-    case 1: return launch_os<M, 1>(sample_kind, a, s);
-    case 2: return launch_os<M, 2>(sample_kind, a, s);
-    default: return launch_os<M, 4>(sample_kind, a, s);
-    }
+    return bank_launch<chan_tile_kernel<M, OS, U8, BLK>, BLK>(lds, lds, a.ntiles, a.H, s, a);
 }
 
 }  // namespace
 
 int chan_launch(int M, int sample_kind, ChanArgs a, hipStream_t s) {
     if (!chan_size_ok((size_t)M) || !chan_block_ok(M, a)) return SDRGPU_ERR_INVALID;
-    switch (M) {
-    case 2: return launch_m<2>(sample_kind, a, s);
-    case 4: return launch_m<4>(sample_kind, a, s);
-    case 8: return launch_m<8>(sample_kind, a, s);
-    case 16: return launch_m<16>(sample_kind, a, s);
-    case 32: return launch_m<32>(sample_kind, a, s);
-    case 64: return launch_m<64>(sample_kind, a, s);
-    case 128: return launch_m<128>(sample_kind, a, s);
-    case 256: return launch_m<256>(sample_kind, a, s);
-    case 512: return launch_m<512>(sample_kind, a, s);
-    case 1024: return launch_m<1024>(sample_kind, a, s);
-    case 2048: return launch_m<2048>(sample_kind, a, s);
-    default: return launch_m<4096>(sample_kind, a, s);
-    }
+    return bank_dispatch(M, a.os, [&]<int MM, int OS>() {
+        return sample_kind == SDRGPU_CU8 ? launch_kind<MM, OS, true>(a, s) : launch_kind<MM, OS, false>(a, s);
+    });
 }
 
 }  // namespace sdrgpu

@@ -45,28 +45,13 @@ template <int TILE>
 constexpr int kChanGenChunk = TILE > 4096 ? 4 : 8;
 #endif
 
-// dynamic LDS a tile may ask for: the engine's image (lp) or the pitched one, whichever is larger
-template <int TILE>
-constexpr size_t kLdsCap = TILE > 4096 ? 160 * 1024 : 48 * 1024;
-
-template <int TILE>
-size_t tile_lds_bytes(const ChanGenPlan& g) {
-    return std::max(lp_bytes<TILE>(g.F * g.M), (size_t)g.F * g.pitch * sizeof(float2));
-}
-
 template <int OS, bool U8, int BLK, int TILE>
 __global__ __launch_bounds__(BLK) void chan_gen_kernel(ChanArgs a, ChanGenPlan g) {
     constexpr int PER = TILE / BLK;  // points per lane
     constexpr int CH = kChanGenChunk<TILE>;
     extern __shared__ float2 lds[];  // tile_lds_bytes
     const int t = threadIdx.x;
-    if (blockIdx.x >= a.ntiles) {
-        // history carry: hist_next[j] = stream sample n_in - H + j
-        const long nb = gridDim.x - a.ntiles;
-        for (long j = (long)(blockIdx.x - a.ntiles) * BLK + t; j < a.H; j += nb * BLK)
-            a.hist_next[j] = stream_sample<U8>(a, a.n_in - a.H + j);
-        return;
-    }
+    if (blockIdx.x >= a.ntiles) return chan_carry<U8, BLK>(a, t);
     const int M = g.M, F = g.F, L = F * M;
     const int D = M / OS;  // frame stride
     const long f0 = (long)blockIdx.x * F;
@@ -137,9 +122,8 @@ __global__ __launch_bounds__(BLK) void chan_gen_kernel(ChanArgs a, ChanGenPlan g
         if (p < L && f < nf) {
             float2 y = lds[f * g.pitch + k];
             if constexpr (OS > 1) {
-                // baseband centring: rot(k, m) = (-j)^(4/OS k (m + 1)), m + 1 = a.rot0 + f0 + f mod OS
-                const int e = (k * (int)((a.rot0 + f0 + f) & (OS - 1)) & (OS - 1)) * (4 / OS);
-                y = rot_quarter(y, e);
+                // baseband centring by rot(k, m), m + 1 = a.rot0 + f0 + f mod OS
+                y = rot_quarter(y, rot_exponent<OS>(k, (int)(a.rot0 + f0 + f)));
             }
             a.out[(long)k * a.ld_out + f0 + f] = y;
         }
@@ -148,16 +132,9 @@ __global__ __launch_bounds__(BLK) void chan_gen_kernel(ChanArgs a, ChanGenPlan g
 
 template <int OS, bool U8, int BLK, int TILE>
 int launch_tile(const ChanGenPlan& g, ChanArgs a, hipStream_t s) {
-    static const bool attr = hipFuncSetAttribute((const void*)chan_gen_kernel<OS, U8, BLK, TILE>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)kLdsCap<TILE>) == hipSuccess;
-    if (!attr) return SDRGPU_ERR_LAUNCH;
     a.ntiles = (unsigned)ceil_div(a.nframes, (long)g.F);
-    const long ncarry = std::min<long>(ceil_div(a.H, (long)BLK), 128);
-    hipLaunchKernelGGL((chan_gen_kernel<OS, U8, BLK, TILE>), dim3(a.ntiles + (unsigned)ncarry),
-                       dim3(BLK), tile_lds_bytes<TILE>(g), s, a, g);
-    SDRGPU_LAUNCH_CHECK();
-    return SDRGPU_OK;
+    return bank_launch<chan_gen_kernel<OS, U8, BLK, TILE>, BLK>(tile_lds_bytes<TILE>(g), kLdsCap<TILE>,
+                                                                a.ntiles, a.H, s, a, g);
 }
 
 template <int OS, bool U8>
@@ -179,24 +156,7 @@ bool chan_gen_plan(size_t M, ChanGenPlan& g) {
     g.tile = g.M >= kChanGenBigMinM ? 16384 : 4096;
     g.F = g.tile / g.M;
     g.df.set(g.F);
-    // 32 consecutive lanes of the transposed read (f fastest, then k) read f pitch + k: the first
-    // pitch from M on under which the tile's first 32 lanes share the fewest 8-byte bank pairs
-    // (none where F >= 32, an odd pitch, or F divides 32; a pitch equal to an M that is a
-    // multiple of 32 would put all frames of a channel on one pair)
-    int fewest = 33;
-    for (int pitch = g.M; pitch < g.M + 32; ++pitch) {
-        unsigned pairs = 0;
-        int shared = 0;
-        for (int p = 0; p < 32 && p < g.F * g.M; ++p) {
-            const unsigned bit = 1u << ((p % g.F * pitch + p / g.F) & 31);
-            shared += (pairs & bit) != 0;
-            pairs |= bit;
-        }
-        if (shared < fewest) {
-            fewest = shared;
-            g.pitch = pitch;
-        }
-    }
+    g.pitch = bank_pitch(g.M, g.F);  // of the image the transposed store reads
     return g.tile > 4096 ? tile_lds_bytes<16384>(g) <= kLdsCap<16384>
                          : tile_lds_bytes<4096>(g) <= kLdsCap<4096>;
 }

@@ -31,26 +31,9 @@
 
 #include <hip/hip_runtime.h>
 
-// The kernel runs tile_fft inside its loop over rounds.  Everything tile_fft derives from the
-// lane index -- some hundred LDS and twiddle indices over its passes -- is invariant in that
-// loop, the compiler moves all of it in front of the loop, and the 1024-lane instantiations
-// (128 VGPRs) then spill it.  Inside sdrgpu::fftd this file therefore lets `threadIdx.x` read
-// the lane index through an empty asm, once per pass: the same value, recomputed where it is
-// used.  fft_tile.hpp is included as it is; chan.hip and fft.hip compile it unchanged.
-namespace sdrgpu {
-namespace fftd {
-struct PerUseLaneIndex {
-    struct X {
-        __device__ __forceinline__ operator int() const {
-            int v = (int)__builtin_amdgcn_workitem_id_x();
-            asm volatile("" : "+v"(v));
-            return v;
-        }
-    } x;
-};
-static constexpr PerUseLaneIndex threadIdx{};
-}  // namespace fftd
-}  // namespace sdrgpu
+// tile_fft runs inside the kernel's loop over rounds: inside sdrgpu::fftd `threadIdx.x` reads the
+// lane index once per use (lane_index_per_use.hpp, before the tile headers).
+#include "lane_index_per_use.hpp"
 
 #include "chan_device.hpp"
 #include "fft_tile.hpp"
@@ -73,13 +56,6 @@ struct SynthTile {
     static constexpr int LDS = G * PITCH > T + T / 16 ? G * PITCH : T + T / 16;  // float2
 };
 
-// frame j of channel k of the history followed by the block; frames the block does not hold are
-// zero (they reach only samples past the block's end, which are not stored)
-__device__ __forceinline__ float2 synth_frame(const SynthArgs& a, int k, long j) {
-    const float2* p = j < 0 ? a.hist + ((long)k * a.HQ + a.HQ + j) : a.in + ((long)k * a.ld_in + j);
-    return j < a.nframes ? *p : make_float2(0.f, 0.f);
-}
-
 template <int M, int OS, int BLK>
 __global__ __launch_bounds__(BLK) void synth_tile_kernel(SynthArgs a) {
     using Tile = SynthTile<M, BLK>;
@@ -87,16 +63,7 @@ __global__ __launch_bounds__(BLK) void synth_tile_kernel(SynthArgs a) {
     constexpr int D = M / OS;  // output samples per frame
     extern __shared__ float2 lds[];  // SynthTile::LDS
     const int t = threadIdx.x;
-    if (blockIdx.x >= a.ntiles) {
-        // history carry: hist_next[k][i] = frame nframes - HQ + i of row k
-        const long nb = gridDim.x - a.ntiles, tot = (long)M * a.HQ;
-        for (long e = (long)(blockIdx.x - a.ntiles) * BLK + t; e < tot; e += nb * BLK) {
-            const int k = (int)(e / a.HQ);
-            const long i = e - (long)k * a.HQ;
-            a.hist_next[e] = synth_frame(a, k, a.nframes - a.HQ + i);
-        }
-        return;
-    }
+    if (blockIdx.x >= a.ntiles) return synth_carry<BLK>(a, M, t);
     const int Q = a.Q;
     const long o0 = (long)blockIdx.x * T;      // first output sample of the tile, of the block
     const long j0 = o0 / D - (Q - 1);          // oldest frame that reaches it, of the block
@@ -116,9 +83,8 @@ __global__ __launch_bounds__(BLK) void synth_tile_kernel(SynthArgs a) {
             const long j = j0 + u0 + f;
             float2 v = synth_frame(a, k, j);
             if constexpr (OS > 1) {
-                // conj(rot(k, m)) = (-j)^(-(4/OS) k (m + 1)), m + 1 = a.rot0 + j (j >= -(Q - 1))
-                const int e = (k * (int)((a.rot0 + j + Q) & (OS - 1)) & (OS - 1)) * (4 / OS);
-                v = rot_quarter(v, (4 - e) & 3);
+                // conj(rot(k, m)), m + 1 = a.rot0 + j mod OS (+ Q, a multiple of OS: j >= -(Q - 1))
+                v = rot_quarter(v, (4 - rot_exponent<OS>(k, (int)(a.rot0 + j + Q))) & 3);
             }
             lds[f * PITCH + k] = v;
         }
@@ -224,51 +190,18 @@ __global__ __launch_bounds__(BLK) void synth_tile_kernel(SynthArgs a) {
 
 template <int M, int OS>
 int launch_os(SynthArgs a, hipStream_t s) {
-    if constexpr (OS > M) return SDRGPU_ERR_INVALID;
-    else {
-        constexpr int BLK = M >= kSynthBigMinM ? 1024 : kFftBlock;
-        using Tile = SynthTile<M, BLK>;
-        constexpr size_t lds = (size_t)Tile::LDS * sizeof(float2);
-        static const bool attr = hipFuncSetAttribute((const void*)synth_tile_kernel<M, OS, BLK>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     (int)lds) == hipSuccess;
-        if (!attr) return SDRGPU_ERR_LAUNCH;
-        a.ntiles = (unsigned)ceil_div(a.n_out, (long)Tile::T);
-        const long ncarry = std::min<long>(ceil_div((long)M * a.HQ, (long)BLK), 128);
-        hipLaunchKernelGGL((synth_tile_kernel<M, OS, BLK>), dim3(a.ntiles + (unsigned)ncarry), dim3(BLK),
-                           lds, s, a);
-        SDRGPU_LAUNCH_CHECK();
-        return SDRGPU_OK;
-    }
-}
-
-template <int M>
-int launch_m(const SynthArgs& a, hipStream_t s) {
-    switch (a.os) {
-    case 1: return launch_os<M, 1>(a, s);
-    case 2: return launch_os<M, 2>(a, s);
-    default: return launch_os<M, 4>(a, s);
-    }
+    constexpr int BLK = M >= kSynthBigMinM ? 1024 : kFftBlock;
+    using Tile = SynthTile<M, BLK>;
+    constexpr size_t lds = (size_t)Tile::LDS * sizeof(float2);
+    a.ntiles = (unsigned)ceil_div(a.n_out, (long)Tile::T);
+    return bank_launch<synth_tile_kernel<M, OS, BLK>, BLK>(lds, lds, a.ntiles, (long)M * a.HQ, s, a);
 }
 
 }  // namespace
 
 int synth_launch(int M, SynthArgs a, hipStream_t s) {
     if (!chan_size_ok((size_t)M) || !synth_block_ok(M, a)) return SDRGPU_ERR_INVALID;
-    switch (M) {
-    case 2: return launch_m<2>(a, s);
-    case 4: return launch_m<4>(a, s);
-    case 8: return launch_m<8>(a, s);
-    case 16: return launch_m<16>(a, s);
-    case 32: return launch_m<32>(a, s);
-    case 64: return launch_m<64>(a, s);
-    case 128: return launch_m<128>(a, s);
-    case 256: return launch_m<256>(a, s);
-    case 512: return launch_m<512>(a, s);
-    case 1024: return launch_m<1024>(a, s);
-    case 2048: return launch_m<2048>(a, s);
-    default: return launch_m<4096>(a, s);
-    }
+    return bank_dispatch(M, a.os, [&]<int MM, int OS>() { return launch_os<MM, OS>(a, s); });
 }
 
 }  // namespace sdrgpu

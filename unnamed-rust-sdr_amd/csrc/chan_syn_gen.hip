@@ -33,24 +33,9 @@
 
 #include <hip/hip_runtime.h>
 
-// As chan_syn.hip: the engine runs inside the loop over rounds, and everything it derives from
-// the lane index is invariant there.  Inside sdrgpu::fftd `threadIdx.x` therefore reads the lane
-// index through an empty asm, once per use, so that the indices are recomputed where they are
-// used and not kept in registers across the rounds.  fft_gen_tile.hpp is included as it is.
-namespace sdrgpu {
-namespace fftd {
-struct PerUseLaneIndex {
-    struct X {
-        __device__ __forceinline__ operator int() const {
-            int v = (int)__builtin_amdgcn_workitem_id_x();
-            asm volatile("" : "+v"(v));
-            return v;
-        }
-    } x;
-};
-static constexpr PerUseLaneIndex threadIdx{};
-}  // namespace fftd
-}  // namespace sdrgpu
+// As chan_syn.hip: the engine runs inside the loop over rounds, so inside sdrgpu::fftd
+// `threadIdx.x` reads the lane index once per use (lane_index_per_use.hpp, before the tile headers).
+#include "lane_index_per_use.hpp"
 
 #include "chan_device.hpp"
 
@@ -79,22 +64,6 @@ constexpr int kSynthGenAcc = TILE > 4096 ? SDRGPU_SYNTH_GEN_BIG_ACC : 16;
 // row loads of a lane in flight at a time (not varied: chosen for the registers, not by A/B)
 constexpr int kSynthGenChunk = 8;
 
-// dynamic LDS a tile may ask for: the engine's image (lp) or the pitched one, whichever is larger
-template <int TILE>
-constexpr size_t kLdsCap = TILE > 4096 ? 160 * 1024 : 48 * 1024;
-
-template <int TILE>
-size_t tile_lds_bytes(const SynthGenPlan& g) {
-    return std::max(lp_bytes<TILE>(g.F * g.M), (size_t)g.F * g.pitch * sizeof(float2));
-}
-
-// frame j of channel k of the history followed by the block; frames the block does not hold are
-// zero (they reach only samples past the block's end, which are not stored)
-__device__ __forceinline__ float2 synth_frame(const SynthArgs& a, int k, long j) {
-    const float2* p = j < 0 ? a.hist + ((long)k * a.HQ + a.HQ + j) : a.in + ((long)k * a.ld_in + j);
-    return j < a.nframes ? *p : make_float2(0.f, 0.f);
-}
-
 template <int OS, int BLK, int TILE>
 __global__ __launch_bounds__(BLK) void synth_gen_kernel(SynthArgs a, SynthGenPlan g) {
     constexpr int PER = TILE / BLK;  // points per lane
@@ -103,16 +72,7 @@ __global__ __launch_bounds__(BLK) void synth_gen_kernel(SynthArgs a, SynthGenPla
     constexpr int CH = kSynthGenChunk;
     extern __shared__ float2 lds[];  // tile_lds_bytes
     const int t = (int)::threadIdx.x;
-    if (blockIdx.x >= a.ntiles) {
-        // history carry: hist_next[k][i] = frame nframes - HQ + i of row k
-        const long nb = gridDim.x - a.ntiles, tot = (long)g.M * a.HQ;
-        for (long e = (long)(blockIdx.x - a.ntiles) * BLK + t; e < tot; e += nb * BLK) {
-            const int k = (int)(e / a.HQ);
-            const long i = e - (long)k * a.HQ;
-            a.hist_next[e] = synth_frame(a, k, a.nframes - a.HQ + i);
-        }
-        return;
-    }
+    if (blockIdx.x >= a.ntiles) return synth_carry<BLK>(a, g.M, t);
     const int M = g.M, F = g.F, FM = F * M;
     const int D = M / OS;  // output samples per frame
     const int Q = a.Q;
@@ -140,9 +100,8 @@ __global__ __launch_bounds__(BLK) void synth_gen_kernel(SynthArgs a, SynthGenPla
                 const long j = j0 + u0 + f;
                 float2 v = synth_frame(a, k, j);
                 if constexpr (OS > 1) {
-                    // conj(rot(k, m)) = (-j)^(-(4/OS) k (m + 1)), m + 1 = a.rot0 + j (j >= -(Q - 1))
-                    const int e = (k * (int)((a.rot0 + j + Q) & (OS - 1)) & (OS - 1)) * (4 / OS);
-                    v = rot_quarter(v, (4 - e) & 3);
+                    // conj(rot(k, m)), m + 1 = a.rot0 + j mod OS (+ Q, a multiple of OS: j >= -(Q - 1))
+                    v = rot_quarter(v, (4 - rot_exponent<OS>(k, (int)(a.rot0 + j + Q))) & 3);
                 }
                 lds[f * g.pitch + k] = v;
             }
@@ -209,16 +168,9 @@ template <int OS, int TILE>
 int launch_tile(const SynthGenPlan& g, SynthArgs a, hipStream_t s) {
     constexpr int BLK = kSynthGenBlock<TILE>;
     constexpr int S = kSynthGenAcc<TILE> * BLK;
-    static const bool attr = hipFuncSetAttribute((const void*)synth_gen_kernel<OS, BLK, TILE>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)kLdsCap<TILE>) == hipSuccess;
-    if (!attr) return SDRGPU_ERR_LAUNCH;
     a.ntiles = (unsigned)ceil_div(a.n_out, (long)S);
-    const long ncarry = std::min<long>(ceil_div((long)g.M * a.HQ, (long)BLK), 128);
-    hipLaunchKernelGGL((synth_gen_kernel<OS, BLK, TILE>), dim3(a.ntiles + (unsigned)ncarry), dim3(BLK),
-                       tile_lds_bytes<TILE>(g), s, a, g);
-    SDRGPU_LAUNCH_CHECK();
-    return SDRGPU_OK;
+    return bank_launch<synth_gen_kernel<OS, BLK, TILE>, BLK>(tile_lds_bytes<TILE>(g), kLdsCap<TILE>, a.ntiles,
+                                                             (long)g.M * a.HQ, s, a, g);
 }
 
 template <int OS>
@@ -236,23 +188,7 @@ bool synth_gen_plan(size_t M, unsigned os, SynthGenPlan& g) {
     g.F = g.tile / g.M;
     g.df.set(g.F);
     g.dd.set(g.M / g.os);
-    // 32 consecutive lanes of the transposed load (f fastest, then k) write f pitch + k: the
-    // first pitch from M on under which the tile's first 32 lanes share the fewest 8-byte bank
-    // pairs (chan_gen_plan's search; the access is its transposed read)
-    int fewest = 33;
-    for (int pitch = g.M; pitch < g.M + 32; ++pitch) {
-        unsigned pairs = 0;
-        int shared = 0;
-        for (int p = 0; p < 32 && p < g.F * g.M; ++p) {
-            const unsigned bit = 1u << ((p % g.F * pitch + p / g.F) & 31);
-            shared += (pairs & bit) != 0;
-            pairs |= bit;
-        }
-        if (shared < fewest) {
-            fewest = shared;
-            g.pitch = pitch;
-        }
-    }
+    g.pitch = bank_pitch(g.M, g.F);  // of the image the transposed load writes
     return g.tile > 4096 ? tile_lds_bytes<16384>(g) <= kLdsCap<16384>
                          : tile_lds_bytes<4096>(g) <= kLdsCap<4096>;
 }
