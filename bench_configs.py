@@ -44,7 +44,7 @@ HBM_GBS = 8000.0
 
 def parse():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="all", choices=["c1", "c3", "c4", "c5", "c2u8", "c2host", "c2pinned", "src", "ex", "fm", "chan", "synth", "src_rows", "all"])
+    ap.add_argument("--config", default="all", choices=["c1", "c3", "c4", "c5", "c2u8", "c2host", "c2pinned", "src", "ex", "fm", "chan", "synth", "src_rows", "polyfir", "all"])
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--c3-log2n", type=int, default=28)
@@ -887,6 +887,100 @@ def bench_src_rows(args):
     return lines
 
 
+# ------------------------------------------------------------------------------ polyfir
+def polyfir_spot_check(pyoracle, h, L, D, x, y, s0, w=4096):
+    """max |y - oracle| / rms over the outputs whose windows lie in x[s0 - pre, s0 + w): the
+    oracle's Fir + Decimate on that stretch zero-stuffed (s0 and pre multiples of D, so the
+    stretch keeps the stream's decimation phase), without the outputs its zero history reaches."""
+    T = -(-h.size // L)
+    pre = min(s0, -(-T // D) * D)
+    seg = x[s0 - pre:s0 + w]
+    u = np.zeros(seg.size * L, seg.dtype)
+    u[::L] = seg
+    ref = pyoracle.Fir(h, D, sample_kind=1 if np.iscomplexobj(seg) else 0).process(u)
+    m0 = (s0 - pre) * L // D
+    skip = 0 if pre == s0 else -(-T * L // D) + 1
+    got = y[m0 + skip:m0 + ref.size]
+    ref = ref[skip:]
+    rms = float(np.sqrt(np.mean(np.abs(ref.astype(np.complex128)) ** 2)))
+    return float(np.max(np.abs(got.astype(np.complex128) - ref)) / rms)
+
+
+def bench_polyfir(args):
+    """The rational-rate polyphase FIR (sdrgpu_polyfir_process_dev): device-resident rows,
+    hipEvents on the handle's stream around the whole call, state carried call to call.  Shapes
+    (a)-(c) alternate with the sinc converter's rows call doing the same job (SampleRateRows at
+    the same ratio), three repetitions each; (d) is one c64 stream.  The first call of every shape
+    is checked against the oracle on two stretches of one row."""
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import pyoracle
+    import scipy.signal as ss
+    from sdrgpu import filter as gfilter, resample
+    from sdrgpu.device import DeviceBuffer, synchronize
+    CT = resample.ConverterType
+    F32, C64 = 0, 1
+    lines = []
+    for tag, rows, nf, L, D, K, kind, conv in (("a", 18, 1 << 20, 1, 3, 97, F32, CT.SincBestQuality),
+                                               ("b", 9, 1 << 22, 18, 25, 433, F32, CT.SincFastest),
+                                               ("c", 1024, 1 << 16, 9, 25, 226, F32, CT.SincFastest),
+                                               ("d", 1, 1 << 26, 2, 15, 361, C64, None)):
+        h = (ss.firwin(K, 0.9 / max(L, D)) * L).astype(np.float32)
+        if kind == C64:
+            xr = np.tile(cplx_pattern(1 << 22, 23), nf >> 22).reshape(rows, nf)
+        else:
+            xr = np.random.default_rng(23).standard_normal((rows, nf), dtype=np.float32)
+        elem = xr.dtype.itemsize
+        x_dev = DeviceBuffer.from_numpy(xr)
+        n_out = nf * L // D
+        cap = n_out + 1  # a later call of the carried stream may return one more
+        y_dev = DeviceBuffer(elem * rows * cap, dtype=xr.dtype)
+        f = gfilter.PolyFir(h, L, D, nch=rows, sample_kind=kind)
+        assert f.process_dev(x_dev.ptr, nf, nf, y_dev.ptr, cap) == n_out
+        f.sync()
+        ch = rows // 2
+        y = y_dev.download(n_out, xr.dtype, offset_bytes=elem * ch * cap)
+        worst = max(polyfir_spot_check(pyoracle, h, L, D, xr[ch], y, s0)
+                    for s0 in (0, (nf // 2) // D * D))
+        del y
+
+        def step_poly():
+            f.process_dev(x_dev.ptr, nf, nf, y_dev.ptr, cap)
+
+        ms_poly, ms_sinc = [], []
+        if conv is not None:
+            ratio = L / D
+            scap = int(nf * ratio) + 16
+            y_sinc = DeviceBuffer(4 * rows * scap, dtype=np.float32)
+            r = resample.SampleRateRows(conv, rows)
+
+            def step_sinc():
+                r.process_dev(ratio, x_dev.ptr, nf, nf, y_sinc.ptr, scap, scap)
+        del xr
+        for _ in range(3):
+            ms_poly.append(time_events(step_poly, f.stream(), args.steps, args.warmup,
+                                       lambda: (f.sync(), synchronize()))[1])
+            if conv is not None:
+                ms_sinc.append(time_events(step_sinc, r.stream(), args.steps, args.warmup,
+                                           lambda: (r.sync(), synchronize()))[1])
+        ms = float(np.mean(ms_poly))
+        line = {"config": f"polyfir ({tag}): {L}/{D}, {K} taps, {rows} rows x {nf} "
+                          f"{'c64' if kind == C64 else 'f32'} samples per call",
+                "metric": "input Msamples/s (all rows)",
+                "value": round(rows * nf / (ms * 1e-3) / 1e6, 1),
+                "polyfir_ms": [round(v, 4) for v in ms_poly],
+                "roofline": roof(elem * (1 + L / D), rows * nf, ms),
+                "products_per_output": -(-K // L), "outputs_per_row": n_out,
+                "spot_check_max_over_rms": worst}
+        if conv is not None:
+            line["sinc_rows_ms"] = [round(v, 4) for v in ms_sinc]
+            line["sinc_converter"] = "SincBestQuality" if conv == CT.SincBestQuality else "SincFastest"
+            line["speedup_mean"] = round(float(np.mean(ms_sinc)) / ms, 1)
+            del y_sinc, r
+        lines.append(line)
+        del x_dev, y_dev, f
+    return lines
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -899,7 +993,7 @@ def main():
         r = {"c1": bench_c1, "c3": bench_c3, "c4": bench_c4, "c5": bench_c5, "c2u8": bench_c2u8,
              "c2host": bench_c2host, "c2pinned": bench_c2pinned, "src": bench_src, "ex": bench_ex,
              "fm": bench_fm, "chan": bench_chan, "synth": bench_synth,
-             "src_rows": bench_src_rows}[c](args)
+             "src_rows": bench_src_rows, "polyfir": bench_polyfir}[c](args)
         for line in (r if isinstance(r, list) else [r]):
             if line is not None:
                 print(json.dumps(line), flush=True)

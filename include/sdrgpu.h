@@ -163,8 +163,8 @@ int sdrgpu_fir_process(sdrgpu_fir* h, const void* in, size_t n_in, void* out,
  * shifted): the handle then filters a device copy of the input, so the results are those of an
  * out-of-place call (the kernels store output tiles while other workgroups still read the
  * input under them).  The same holds for sdrgpu_firbank_process_dev, sdrgpu_chan_process_dev,
- * sdrgpu_synth_process_dev, sdrgpu_fft_exec_dev, sdrgpu_rfft_exec_dev and
- * sdrgpu_stft_process_dev. */
+ * sdrgpu_synth_process_dev, sdrgpu_polyfir_process_dev, sdrgpu_fft_exec_dev,
+ * sdrgpu_rfft_exec_dev and sdrgpu_stft_process_dev. */
 int sdrgpu_fir_process_dev(sdrgpu_fir* h, const void* d_in, size_t n_in, void* d_out,
                            size_t out_cap, size_t* n_out);
 /* HOST pointers, asynchronous (the Block adapter's producer/consumer split,
@@ -349,6 +349,58 @@ int sdrgpu_synth_sync(sdrgpu_synth* h);
 int sdrgpu_synth_reset(sdrgpu_synth* h);
 int sdrgpu_synth_clone(const sdrgpu_synth* h, sdrgpu_synth** out);
 void sdrgpu_synth_destroy(sdrgpu_synth* h);
+
+/* Rational-rate polyphase FIR ("upfirdn"): up by L, FIR, keep every D-th sample.
+ * Parameters: real f32 taps h[0..K), up = L >= 1, down = D >= 1.  Per row, over the stream so far:
+ *   1. zero-stuff: u[i] = x[i / L] if L divides i, else 0 (the first input lands on u[0]);
+ *   2. v = signal.filter(h) on u, the reference's Fir with zero history (src/filter/fir.rs:23-32);
+ *   3. .decimate(..) by D, the reference's Decimate (src/signal/adapters/mod.rs:30-37), which
+ *      keeps v at indices D-1, 2D-1, ...
+ * So with j = m*D + D-1, p = j mod L, q = j div L:
+ *   y[m] = sum_{t >= 0, p + L*t < K} h[p + L*t] * x[q - t],   x[<0] = 0.
+ * Only the kept outputs and the non-zero products are computed.  After n inputs in total exactly
+ * floor(n*L / D) outputs exist; a call returns the ones not yet returned, possibly none.  There
+ * is no latency and no end-of-input flush; the output rate is rate*L/D.  No gain is applied: the
+ * caller scales the taps by L, as with upfirdn.  gcd(L, D) > 1 is allowed and is not reduced (it
+ * selects different taps).  With up = 1 the definition is sdrgpu_fir's with decim = D (the
+ * results agree within the parity tolerance, not bit for bit).  A phase with no tap (K < L) gives
+ * exact zeros.  Only real products are formed and a padding tap never multiplies a sample, so an
+ * inf / NaN sample x[q0] reaches exactly the outputs with 0 <= j - L*q0 < K, as in the reference.
+ * Kinds: samples SDRGPU_F32 or SDRGPU_C64, taps f32; outputs have the samples' kind.  SDRGPU_CU8
+ * samples are SDRGPU_ERR_UNSUPPORTED.
+ * Layout: rows as in sdrgpu_firbank: row c starts at in + c*ld_in (samples); nch = 1 is the single
+ * stream.  ld_out is both the output row stride and the capacity: n_out > ld_out returns
+ * SDRGPU_ERR_OUTPUT_CAP with no state touched (*n_out is set); ld_in < n_in is SDRGPU_ERR_INVALID.
+ * Argument checks, before the device is looked at: a null pointer, ntaps, up, down or nch equal
+ * to 0, or a kind other than the three enum values: SDRGPU_ERR_INVALID; up or down > 4096,
+ * ceil(ntaps/up) > 1024, nch > 65536 or CU8 samples: SDRGPU_ERR_UNSUPPORTED.
+ * Row r of an nch-row handle is bit-identical to an nch = 1 handle fed row r, and any partition
+ * of a stream into calls -- n_in = 0 and calls that produce nothing included -- is bit-identical:
+ * an output's summation order depends on m only.  State: the last ceil(K/L) - 1 inputs per row
+ * on the device and the input count; reset returns to the zero state, a clone keeps taps, ratio,
+ * count and history and gets its own stream.  d_out may overlap d_in (see
+ * sdrgpu_fir_process_dev).
+ * sdrgpu_polyfir_plan is the handle-free bookkeeping: outputs [*first_out, *first_out + *n_out)
+ * become available when n_in inputs follow `consumed` inputs (exact for consumed beyond 2^48
+ * with up = 4096). */
+typedef struct sdrgpu_polyfir sdrgpu_polyfir;
+
+int sdrgpu_polyfir_create(int device, int sample_kind, const float* taps, size_t ntaps,
+                          uint32_t up, uint32_t down, size_t nch, sdrgpu_polyfir** out);
+int sdrgpu_polyfir_plan(uint32_t up, uint32_t down, size_t consumed, size_t n_in,
+                        size_t* first_out, size_t* n_out);
+int sdrgpu_polyfir_get_ratio(const sdrgpu_polyfir* h, uint32_t* up, uint32_t* down);
+int sdrgpu_polyfir_set_stream(sdrgpu_polyfir* h, void* hip_stream);
+int sdrgpu_polyfir_get_stream(const sdrgpu_polyfir* h, void** hip_stream);
+int sdrgpu_polyfir_output_len(const sdrgpu_polyfir* h, size_t n_in, size_t* n_out);
+int sdrgpu_polyfir_process(sdrgpu_polyfir* h, const void* in, size_t ld_in, size_t n_in,
+                           void* out, size_t ld_out, size_t* n_out);
+int sdrgpu_polyfir_process_dev(sdrgpu_polyfir* h, const void* d_in, size_t ld_in, size_t n_in,
+                               void* d_out, size_t ld_out, size_t* n_out);
+int sdrgpu_polyfir_sync(sdrgpu_polyfir* h);
+int sdrgpu_polyfir_reset(sdrgpu_polyfir* h);
+int sdrgpu_polyfir_clone(const sdrgpu_polyfir* h, sdrgpu_polyfir** out);
+void sdrgpu_polyfir_destroy(sdrgpu_polyfir* h);
 
 /* =====================================================================================
  * FFT.

@@ -448,6 +448,82 @@ impl Drop for Synthesizer {
     }
 }
 
+// ------------------------------------------------------------- rational-rate FIR
+
+/// Rational-rate polyphase FIR over `nch` rows (include/sdrgpu.h `sdrgpu_polyfir`): zero-stuff by
+/// `up`, `Fir` with the real `taps` (src/filter/fir.rs:23-32), `Decimate` by `down`
+/// (src/signal/adapters/mod.rs:30-37), with only the kept outputs and the non-zero products
+/// computed.  `floor(n * up / down)` outputs exist after `n` inputs per row; a call returns the
+/// ones not yet returned, so any partition of a stream into calls gives the same samples.  No
+/// gain is applied: scale the taps by `up`.
+pub struct PolyFir<A> {
+    h: *mut sys::sdrgpu_polyfir,
+    nch: usize,
+    _sample: std::marker::PhantomData<A>,
+}
+
+unsafe impl<A> Send for PolyFir<A> {}
+
+impl<A: GpuSample> PolyFir<A> {
+    /// `up`, `down`: 1..=4096; `ceil(taps.len() / up) <= 1024`; `nch`: 1..=65536 rows.
+    pub fn new(taps: &[f32], up: u32, down: u32, nch: usize) -> Result<Self> {
+        let mut h = ptr::null_mut();
+        check(unsafe {
+            sys::sdrgpu_polyfir_create(DEVICE, A::KIND, taps.as_ptr(), taps.len(), up, down, nch, &mut h)
+        })?;
+        Ok(PolyFir { h, nch, _sample: std::marker::PhantomData })
+    }
+
+    /// `(up, down)`.
+    pub fn ratio(&self) -> (u32, u32) {
+        let (mut up, mut down) = (0, 0);
+        check(unsafe { sys::sdrgpu_polyfir_get_ratio(self.h, &mut up, &mut down) })
+            .expect("sdrgpu_polyfir_get_ratio");
+        (up, down)
+    }
+
+    /// Outputs per row the next `process` call returns for `n` inputs per row.
+    pub fn output_len(&self, n: usize) -> Result<usize> {
+        let mut m = 0;
+        check(unsafe { sys::sdrgpu_polyfir_output_len(self.h, n, &mut m) })?;
+        Ok(m)
+    }
+
+    /// `rows`: `nch` rows of `n` samples each (leading dimension `n`); `output` gets `nch` rows
+    /// of the returned count (leading dimension that count).
+    pub fn process(&mut self, rows: &[A], n: usize, output: &mut Vec<A>) -> Result<usize> {
+        assert_eq!(rows.len(), self.nch * n);
+        let mut m = self.output_len(n)?;
+        let ld = m.max(1);
+        output.resize(self.nch * ld, A::zero());
+        check(unsafe {
+            sys::sdrgpu_polyfir_process(self.h, rows.as_ptr() as *const _, n.max(1), n,
+                                        output.as_mut_ptr() as *mut _, ld, &mut m)
+        })?;
+        output.truncate(self.nch * m);
+        Ok(m)
+    }
+
+    pub fn reset(&mut self) -> Result<()> {
+        check(unsafe { sys::sdrgpu_polyfir_reset(self.h) })
+    }
+}
+
+impl<A> Clone for PolyFir<A> {
+    // the copy carries the ratio, the input count and the history
+    fn clone(&self) -> Self {
+        let mut h = ptr::null_mut();
+        check(unsafe { sys::sdrgpu_polyfir_clone(self.h, &mut h) }).expect("sdrgpu_polyfir_clone");
+        PolyFir { h, nch: self.nch, _sample: std::marker::PhantomData }
+    }
+}
+
+impl<A> Drop for PolyFir<A> {
+    fn drop(&mut self) {
+        unsafe { sys::sdrgpu_polyfir_destroy(self.h) }
+    }
+}
+
 // ------------------------------------------------------------------ biquad designs
 
 /// The filter designs the PLL and the biquad stage take: `BiquadD` (src/filter/biquad.rs:

@@ -164,6 +164,22 @@ SIGNATURES = [
     ("sdrgpu_synth_reset", c_int, [_H]),
     ("sdrgpu_synth_clone", c_int, [_H, _PH]),
     ("sdrgpu_synth_destroy", None, [_H]),
+    # rational-rate polyphase FIR
+    ("sdrgpu_polyfir_create", c_int,
+     [c_int, c_int, c_void_p, c_size_t, c_uint32, c_uint32, c_size_t, _PH]),
+    ("sdrgpu_polyfir_plan", c_int, [c_uint32, c_uint32, c_size_t, c_size_t, _PS, _PS]),
+    ("sdrgpu_polyfir_get_ratio", c_int, [_H, POINTER(c_uint32), POINTER(c_uint32)]),
+    ("sdrgpu_polyfir_set_stream", c_int, [_H, c_void_p]),
+    ("sdrgpu_polyfir_get_stream", c_int, [_H, _PH]),
+    ("sdrgpu_polyfir_output_len", c_int, [_H, c_size_t, _PS]),
+    ("sdrgpu_polyfir_process", c_int,
+     [_H, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, _PS]),
+    ("sdrgpu_polyfir_process_dev", c_int,
+     [_H, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, _PS]),
+    ("sdrgpu_polyfir_sync", c_int, [_H]),
+    ("sdrgpu_polyfir_reset", c_int, [_H]),
+    ("sdrgpu_polyfir_clone", c_int, [_H, _PH]),
+    ("sdrgpu_polyfir_destroy", None, [_H]),
     # FFT
     ("sdrgpu_fft_plan", c_int, [c_int, c_size_t, _PH]),
     ("sdrgpu_fft_set_stream", c_int, [_H, c_void_p]),

@@ -294,6 +294,104 @@ class FirBank:
         return a.value
 
 
+# -------------------------------------------------------------------------- PolyFir
+class PolyFir:
+    """Rational-rate polyphase FIR ("upfirdn", sdrgpu_polyfir): per row, zero-stuff by `up`,
+    signal.filter(taps) (fir.rs:23-32), .decimate by `down` (adapters/mod.rs:30-37), with only the
+    kept outputs and the non-zero products computed.  floor(n*up/down) outputs exist after n
+    inputs; no gain is applied (scale the taps by `up`).  State carries across blocks."""
+
+    def __init__(self, taps, up: int, down: int, nch: int = 1, sample_kind: int = C64,
+                 device: int = 0, _handle=None):
+        if np.iscomplexobj(np.asarray(taps)):
+            raise _lib.SdrGpuError(_lib.ERR_UNSUPPORTED, "PolyFir: taps must be real")
+        self.taps = np.ascontiguousarray(taps, dtype=np.float32)
+        self.up = int(up)
+        self.down = int(down)
+        self.nch = int(nch)
+        self.sample_kind = sample_kind
+        self.device = device
+        self._h = ctypes.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            check(lib().sdrgpu_polyfir_create(device, sample_kind, self.taps.ctypes.data,
+                                              self.taps.size, self.up, self.down, self.nch,
+                                              ctypes.byref(self._h)), "sdrgpu_polyfir_create")
+
+    def close(self):
+        if self._h:
+            lib().sdrgpu_polyfir_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clone(self) -> "PolyFir":
+        h = ctypes.c_void_p()
+        check(lib().sdrgpu_polyfir_clone(self._h, ctypes.byref(h)), "sdrgpu_polyfir_clone")
+        return PolyFir(self.taps, self.up, self.down, self.nch, self.sample_kind, self.device,
+                       _handle=h)
+
+    def reset(self):
+        check(lib().sdrgpu_polyfir_reset(self._h), "sdrgpu_polyfir_reset")
+
+    def set_stream(self, stream_ptr: Optional[int]):
+        check(lib().sdrgpu_polyfir_set_stream(self._h, stream_ptr), "set_stream")
+
+    def stream(self) -> int:
+        s = ctypes.c_void_p()
+        check(lib().sdrgpu_polyfir_get_stream(self._h, ctypes.byref(s)), "get_stream")
+        return s.value or 0
+
+    def output_len(self, n_in: int) -> int:
+        """Outputs per row the next call produces for n_in inputs."""
+        n = ctypes.c_size_t()
+        check(lib().sdrgpu_polyfir_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
+        return n.value
+
+    def process(self, x) -> np.ndarray:
+        """x: (n,) for nch = 1, else (nch, n) -> (n_out,) or (nch, n_out)."""
+        x = _as_c(x, self.sample_kind)
+        flat = x.ndim == 1 and self.nch == 1
+        if flat:
+            x = x.reshape(1, -1)
+        if x.ndim != 2 or x.shape[0] != self.nch:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "PolyFir.process: shape must be (nch, n)")
+        n_in = x.shape[1]
+        n_out = self.output_len(n_in)
+        out = np.empty((self.nch, max(n_out, 1)), dtype=_np_dtype(self.sample_kind))
+        got = ctypes.c_size_t()
+        check(lib().sdrgpu_polyfir_process(self._h, x.ctypes.data, max(n_in, 1), n_in,
+                                           out.ctypes.data, out.shape[1], ctypes.byref(got)),
+              "sdrgpu_polyfir_process")
+        y = out[:, :got.value]
+        return y[0] if flat else y
+
+    def process_dev(self, d_in_ptr: int, ld_in: int, n_in: int, d_out_ptr: int,
+                    ld_out: int) -> int:
+        got = ctypes.c_size_t()
+        check(lib().sdrgpu_polyfir_process_dev(self._h, d_in_ptr, ld_in, n_in, d_out_ptr,
+                                               ld_out, ctypes.byref(got)),
+              "sdrgpu_polyfir_process_dev")
+        return got.value
+
+    def sync(self):
+        check(lib().sdrgpu_polyfir_sync(self._h), "sdrgpu_polyfir_sync")
+
+
+def polyfir_plan(up: int, down: int, consumed: int, n_in: int):
+    """(first_out, n_out): the outputs that become available when n_in inputs follow `consumed`
+    inputs (sdrgpu_polyfir_plan; no handle, no device)."""
+    first, n = ctypes.c_size_t(), ctypes.c_size_t()
+    check(lib().sdrgpu_polyfir_plan(up, down, consumed, n_in, ctypes.byref(first), ctypes.byref(n)),
+          "sdrgpu_polyfir_plan")
+    return first.value, n.value
+
+
 # ---------------------------------------------------------------------- Channelizer
 class Channelizer:
     """Polyphase channelizer: one wideband stream into nch channel rows.  Channel k is the

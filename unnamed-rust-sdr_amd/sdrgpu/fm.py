@@ -95,7 +95,28 @@ def _convert_rows(sr, ratio, blocks):
         yield y
 
 
-def receivers(wideband, nch: int, taps, oversample: int = 2):
+def _poly_rows(pf, blocks):
+    """Every block of (rows, n) through the PolyFir `pf` (no latency, nothing to flush)."""
+    for x in blocks:
+        y = pf.process(np.ascontiguousarray(x, np.float32))
+        if y.shape[1]:
+            yield y
+
+
+def _exact_ratio(num: float, den: float):
+    """num / den as the fraction in lowest terms, or ERR_UNSUPPORTED where the rates are not
+    whole numbers or the terms pass the PolyFir's limit of 4096."""
+    from fractions import Fraction
+    if num != int(num) or den != int(den) or den <= 0:
+        raise _lib.SdrGpuError(_lib.ERR_UNSUPPORTED, "fm.receivers: rate_taps needs whole-number rates")
+    f = Fraction(int(num), int(den))
+    if f.numerator > 4096 or f.denominator > 4096:
+        raise _lib.SdrGpuError(_lib.ERR_UNSUPPORTED,
+                               f"fm.receivers: {f.numerator}/{f.denominator} is beyond the PolyFir's limits")
+    return f.numerator, f.denominator
+
+
+def receivers(wideband, nch: int, taps, oversample: int = 2, rate_taps=None):
     """`receiver`'s chain for every channel of one wideband capture: `wideband` (c64 or rtl_tcp
     CU8 Signal) -> Signal of (nch, n, 2) f32 blocks, (left, right) at 48 kHz for station k in
     the band centred at +k * rate / nch.  Every stage reads and writes channel rows:
@@ -108,7 +129,12 @@ def receivers(wideband, nch: int, taps, oversample: int = 2):
       de-emphasis Biquad bank of 2 nch rows           -> (mono + diff, mono - diff)
 
     Station k's samples are `receiver`'s stage for stage on channel row k.  oversample must be
-    one the Channelizer offers for nch (1, or 2 / 4 where they divide nch)."""
+    one the Channelizer offers for nch (1, or 2 / 4 where they divide nch).
+
+    rate_taps = (h1, h2) replaces the two sinc converters with rational-rate polyphase FIRs on the
+    caller's taps: PolyFir(h1, up1, down1, nch) with up1/down1 the exact fraction
+    144000 / row rate (ERR_UNSUPPORTED where there is none within the PolyFir's limits), and
+    PolyFir(h2, 1, 3, 2 nch).  The default None leaves the chain above as it is."""
     from .signal import Signal
     if wideband.sample_kind not in (_lib.C64, _lib.CU8):
         raise _lib.SdrGpuError(_lib.ERR_INVALID, "fm.receivers: expects a c64 or CU8 Signal")
@@ -120,6 +146,19 @@ def receivers(wideband, nch: int, taps, oversample: int = 2):
     dev = np.float32(DEVIATION)
     r1 = float(np.float32(48000.0 * 3.0)) / float(np.float32(row_rate))
     r2 = float(np.float32(48000.0)) / float(np.float32(48000.0 * 3.0))
+    if rate_taps is not None:
+        h1, h2 = (np.asarray(h, np.float32) for h in rate_taps)
+        up1, down1 = _exact_ratio(48000.0 * 3.0, row_rate)
+
+    def to_audio(rows):  # main.rs:48
+        if rate_taps is not None:
+            return _poly_rows(_filter.PolyFir(h1, up1, down1, nch, sample_kind=_lib.F32), rows)
+        return _convert_rows(_resample.SampleRateRows(_resample.ConverterType.SincFastest, nch), r1, rows)
+
+    def to_out(rows):  # main.rs:71
+        if rate_taps is not None:
+            return _poly_rows(_filter.PolyFir(h2, 1, 3, 2 * nch, sample_kind=_lib.F32), rows)
+        return _convert_rows(_resample.SampleRateRows(_resample.ConverterType.SincBestQuality, 2 * nch), r2, rows)
 
     def fm():
         chan = _filter.Channelizer(taps, nch, sample_kind=kind, oversample=oversample)
@@ -132,8 +171,7 @@ def receivers(wideband, nch: int, taps, oversample: int = 2):
 
     def stereo():
         pilot = pilot_design().design(48000.0 * 3.0, nch=nch)
-        for a in _convert_rows(_resample.SampleRateRows(
-                _resample.ConverterType.SincFastest, nch), r1, fm()):
+        for a in to_audio(fm()):
             mono, diff, _ = pilot.stereo(a)
             md = np.empty((2 * nch, a.shape[1]), np.float32)
             md[0::2] = mono
@@ -142,8 +180,7 @@ def receivers(wideband, nch: int, taps, oversample: int = 2):
 
     def out():
         bank = deemphasis().design(48000.0, sample_kind=_lib.F32, nch=2 * nch)
-        for md in _convert_rows(_resample.SampleRateRows(
-                _resample.ConverterType.SincBestQuality, 2 * nch), r2, stereo()):
+        for md in to_out(stereo()):
             y = bank.process(np.ascontiguousarray(md))
             yield np.stack([y[0::2] + y[1::2], y[0::2] - y[1::2]], axis=2)
 

@@ -141,6 +141,27 @@ class Signal:
                 phase = (phase + _nsamples(b, sk)) % wait
         return Signal(self._rate, gen, sk)  # Decimate::rate quirk (:38-40)
 
+    def resample_poly(self, up: int, down: int, taps) -> "Signal":
+        """Rational-rate polyphase FIR (filter.PolyFir): zero-stuff by `up`, filter with the real
+        `taps`, keep every `down`-th sample; the rate becomes rate * up / down.  No reference
+        counterpart as one stage: it is .filter(taps).decimate(..) on the zero-stuffed stream."""
+        sk = self.sample_kind
+        if sk == _lib.CU8:
+            raise _lib.SdrGpuError(_lib.ERR_UNSUPPORTED, "resample_poly: CU8 samples")
+        src = self
+
+        def gen():
+            f = None
+            for b in src.blocks():
+                b = np.asarray(b)
+                if f is None:
+                    kind = sk if sk is not None else (_lib.C64 if np.iscomplexobj(b) else _lib.F32)
+                    f = _filter.PolyFir(taps, up, down, 1, sample_kind=kind)
+                y = f.process(b)
+                if y.size:
+                    yield y
+        return Signal(self._rate * up / down, gen, sk)
+
     def resample(self, rate: float) -> "Signal":
         """Signal::resample (src/signal/mod.rs:78-84): SincBestQuality (this library's own
         sinc table)."""
