@@ -519,10 +519,18 @@ int sdrgpu_pll_set_input_kind(sdrgpu_pll* h, int sample_kind);
  * always one serial pass; warm = 0: 4096.  Lengths round up to multiples of 8.  The automatic
  * plan adapts per handle: after a block in which more than half of the segments had to be
  * recomputed (an unlocked loop, e.g. noise with no station), the next 8 blocks run one serial
- * pass and the handle then tries segments again (reset starts over).  A
- * sdrgpu_pll_process_dev call whose output or lock range overlaps its input range (in place)
- * runs one serial pass whatever the plan (the segment kernels re-read inputs after outputs are
- * stored). */
+ * pass and the handle then tries segments again (reset starts over).
+ *
+ * In-place calls: a sdrgpu_pll_process_dev call whose output or lock rows overlap its input rows
+ * gives the results of an out-of-place call, for every overlap.  One serial pass runs in place,
+ * whatever the plan and without counting towards the 8 serial blocks above, where no store can
+ * reach an input still to be read: the overlapping rows (the f32 outputs, or the lock bytes)
+ * have the input rows' pitch in bytes and start at the input rows or before them, by no more
+ * than the gap between one input row's end and the next row's start -- e.g. d_out == d_in with
+ * ld_out = 2 ld_in, each output row inside its own c64 input row.  Every other overlap (d_out ==
+ * d_in with ld_out == ld_in, any forward shift, u8 input under f32 output, ...) first copies
+ * the input span (nch - 1) * ld_in + n samples to a buffer of the handle's, on its stream, and
+ * runs the normal plan on the copy.  d_out overlapping d_locked is SDRGPU_ERR_INVALID. */
 int sdrgpu_pll_set_time_parallel(sdrgpu_pll* h, long seg, long warm);
 /* The segment length (0 = one serial pass) and warm-up a block of n samples would use. */
 int sdrgpu_pll_time_parallel_plan(const sdrgpu_pll* h, size_t n, long* seg, long* warm);
@@ -588,8 +596,12 @@ int sdrgpu_biquad_process_dev(sdrgpu_biquad* h, const void* d_in, size_t ld_in, 
  * bit for bit against the true state and recomputed where they differ.  seg = warm = 0:
  * automatic (warm-up from the filter's slower pole, enough segments to fill the device, none
  * for Identity, an unstable design or a block that gives fewer than two); seg < 0: always
- * one serial pass.  Mirrors sdrgpu_pll_set_time_parallel, in-place calls included (an output
- * range overlapping the input runs one serial pass). */
+ * one serial pass.  Mirrors sdrgpu_pll_set_time_parallel, in-place calls included: a
+ * sdrgpu_biquad_process_dev call whose output rows overlap its input rows gives an out-of-place
+ * call's results for every overlap.  With ld_out == ld_in and d_out at d_in, or before it by no
+ * more than ld_in - n samples (any distance for one channel), one serial pass runs in place;
+ * every other overlap (a forward shift, different leading dimensions, rows reaching into other
+ * rows) filters a device copy of the input span with the normal plan. */
 int sdrgpu_biquad_set_time_parallel(sdrgpu_biquad* h, long seg, long warm);
 /* the (segment, warm-up) a block of n samples per channel would use (segment 0: serial) */
 int sdrgpu_biquad_time_parallel_plan(const sdrgpu_biquad* h, size_t n, long* seg, long* warm);

@@ -456,3 +456,58 @@ def test_pll_time_parallel_adapts_to_misses(sdr, oracle):
     pll.reset()
     pll.process(x[:, :n])
     assert pll.last_time_parallel()[0] > 0
+
+
+def test_pll_in_place_blocks_do_not_use_up_the_serial_stretch(sdr, oracle):
+    """The 8-block serial stretch after a miss-heavy block counts blocks the adapted plan made
+    serial, not blocks an in-place layout made serial anyway: after the miss-heavy block, eight
+    in-place blocks (each output row inside its own input row: one serial pass whatever the
+    plan), then eight out-of-place blocks that must still be serial, then segments again.
+    Outputs and lock flags array_equal to the oracle throughout (src/filter/pll.rs:70-85)."""
+    from sdrgpu.device import DeviceBuffer
+    rng = np.random.default_rng(81)
+    nch, n, blocks = 64, 1 << 14, 18
+    pll = main_rs_design(sdr).design(RATE, nch=nch)
+    pll.set_time_parallel(0, 8)
+    x = fm_channels(rng, nch, n * blocks)
+    outs, lks, plan = [], [], []
+    for b in range(blocks):
+        xb = np.ascontiguousarray(x[:, b * n:(b + 1) * n])
+        if 1 <= b <= 8:
+            dx = DeviceBuffer.from_numpy(xb)
+            dl = DeviceBuffer.empty(nch * 2 * n, np.uint8)
+            pll.process_dev(dx.ptr, n, n, dx.ptr, dl.ptr, 2 * n)
+            pll.sync()
+            o = dx.download(nch * 2 * n, np.float32).reshape(nch, 2 * n)[:, :n]
+            lk = dl.download(dtype=np.uint8).reshape(nch, 2 * n)[:, :n]
+        else:
+            o, lk = pll.process(xb)
+        plan.append(pll.last_time_parallel())
+        outs.append(o)
+        lks.append(lk)
+    assert plan[0][0] > 0 and 2 * plan[0][1] > plan[0][0] * nch, plan[0]
+    assert all(p[0] == 0 for p in plan[1:9]), plan       # in place
+    assert all(p[0] == 0 for p in plan[9:17]), plan      # the whole serial stretch is still to come
+    assert plan[17][0] > 0, plan
+    ref_out, ref_lk = oracle.pll_batch(oracle_params(oracle), x, nthreads=16)
+    check(np.concatenate(outs, axis=1), np.concatenate(lks, axis=1), ref_out, ref_lk, "in place, then adapted")
+
+
+def test_pll_phase_timing_switched_on_after_an_untimed_block(sdr):
+    """sdrgpu_pll_last_phase_ms reads events only a timed time-parallel block has recorded: with
+    timing switched on after an untimed segmented block it returns zeros and no error; the next
+    segmented block is timed."""
+    nch, n = 4, 8192
+    x = fm_channels(np.random.default_rng(82), nch, n)
+    pll = main_rs_design(sdr).design(RATE, nch=nch)
+    pll.set_time_parallel(2048, 1024)
+    pll.process(x)
+    assert pll.last_time_parallel()[0] == 4
+    pll.set_phase_timing(True)
+    assert pll.last_phase_ms() == (0.0, 0.0, 0.0)
+    pll.process(x)
+    ms = pll.last_phase_ms()
+    assert all(v >= 0.0 for v in ms) and sum(ms) > 0.0, ms
+    pll.set_time_parallel(-1)
+    pll.process(x)
+    assert pll.last_phase_ms() == (0.0, 0.0, 0.0)     # a serial block records none

@@ -18,7 +18,7 @@ struct sdrgpu_biquad {
     float c[5] = {1.f, 0.f, 0.f, 0.f, 0.f};
     BiquadState* d_state = nullptr;
     StreamSlot stream;
-    DevBuf stage_in, stage_out;
+    DevBuf stage_in, stage_out, stage_alias;
     TpPlanner tp;  // time-parallel blocks (time_parallel.hpp)
 
     // Warm-up for two trajectories of this recurrence to agree bit for bit: the slower pole of
@@ -68,6 +68,7 @@ struct sdrgpu_biquad {
         d_state = nullptr;
         stage_in.release();
         stage_out.release();
+        stage_alias.release();
         tp.buf.release();
         stream.destroy();
     }
@@ -100,9 +101,13 @@ struct sdrgpu_biquad {
         if (!in || !out || ld_in < n || ld_out < n) return SDRGPU_ERR_INVALID;
         BqSpec sp;
         const size_t sb = sbytes();
-        const bool alias = bytes_overlap(in, rows_span(nch, ld_in, n, sb), out, rows_span(nch, ld_out, n, sb));
-        int st = make_spec((long)n, &sp, alias);
-        if (st) return st;
+        // output rows over the input rows (abi_common.hpp, alias_plan.hpp)
+        const alias::Plan ap = alias::classify(nch, alias_rows(in, ld_in, n, sb), alias_rows(out, ld_out, n, sb));
+        int st;
+        if (ap == alias::Plan::copy_input &&
+            (st = stage_input(stage_alias, in, rows_span(nch, ld_in, n, sb), stream.cur)))
+            return st;
+        if ((st = make_spec((long)n, &sp, ap == alias::Plan::serial_in_place))) return st;
         if (sp.seg > 0)
             return biquad_tp_launch(sk == SDRGPU_C64, (long)nch, c, in, (long)ld_in, (long)n, out,
                                     (long)ld_out, d_state, sp, stream.cur);

@@ -7,6 +7,7 @@
 #include <new>
 #include <utility>
 
+#include "alias_plan.hpp"
 #include "common.hpp"
 #include "time_parallel.hpp"
 
@@ -277,27 +278,39 @@ inline size_t kind_bytes(int kind) { return kind == SDRGPU_C64 ? 8 : (kind == SD
 inline size_t rows_span(size_t rows, size_t ld, size_t n, size_t elem) {
     return rows ? ((rows - 1) * ld + n) * elem : 0;
 }
-// Whether the byte ranges [a, a + na) and [b, b + nb) overlap.  The time-parallel biquad and PLL
-// plans read input samples after outputs were stored (warm-ups reach into the previous segment;
-// the re-run and walk kernels re-read whole segments), so an in-place call takes the serial pass,
-// which reads every chunk before it stores it.
+// Whether the byte ranges [a, a + na) and [b, b + nb) overlap.
 inline bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return na && nb && x < y + nb && y < x + na;
 }
-// The FIR, FFT and STFT kernels store output tiles while other workgroups still read the input
-// under them, so a device input range that overlaps the call's output range is copied to `stage`
-// (on the call's stream, ahead of the kernels) and the copy is read instead: in-place calls give
-// the results of out-of-place ones, at the cost of one device copy of the input.
-inline int unalias_input(DevBuf& stage, const void*& in, size_t in_bytes, const void* out,
-                         size_t out_bytes, hipStream_t s) {
-    if (!bytes_overlap(in, in_bytes, out, out_bytes)) return SDRGPU_OK;
+// Copies the device range [in, in + in_bytes) to `stage` (on the call's stream, ahead of the
+// kernels) and points `in` at the copy.
+inline int stage_input(DevBuf& stage, const void*& in, size_t in_bytes, hipStream_t s) {
     const int st = stage.ensure(in_bytes);
     if (st) return st;
     if (hipMemcpyAsync(stage.ptr, in, in_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
         return SDRGPU_ERR_DEVICE;
     in = stage.ptr;
     return SDRGPU_OK;
+}
+// The FIR, FFT and STFT kernels store output tiles while other workgroups still read the input
+// under them, so a device input range that overlaps the call's output range is copied to `stage`
+// and the copy is read instead: in-place calls give the results of out-of-place ones, at the
+// cost of one device copy of the input.
+inline int unalias_input(DevBuf& stage, const void*& in, size_t in_bytes, const void* out,
+                         size_t out_bytes, hipStream_t s) {
+    if (!bytes_overlap(in, in_bytes, out, out_bytes)) return SDRGPU_OK;
+    return stage_input(stage, in, in_bytes, s);
+}
+// The biquad and the PLL (serial recurrences, one row per lane): an overlapped call runs the
+// serial pass in place only where alias_plan.hpp shows that no store can reach an input byte
+// still to be read -- a chunk's loads precede its stores in one lane's own row, but not across
+// chunks that a shift moves onto each other, nor across the lanes of other rows.  The time-parallel
+// plans never run in place (warm-ups reach into the previous segment; the re-run and walk kernels
+// re-read whole segments after outputs were stored).  Every other overlap copies the input span,
+// row pitch kept, and runs the handle's normal plan on the copy.
+inline alias::Rows alias_rows(const void* base, size_t ld, size_t n, size_t elem) {
+    return alias::Rows{reinterpret_cast<uintptr_t>(base), ld, n, elem};
 }
 
 }  // namespace detail

@@ -67,7 +67,7 @@ struct sdrgpu_pll {
     PllDevParams dp{};
     PllChannelState* d_state = nullptr;
     StreamSlot stream;
-    DevBuf stage_in, stage_out, stage_lock;
+    DevBuf stage_in, stage_out, stage_lock, stage_alias;
     AsyncD2H async;
     TpPlanner tp;  // time-parallel segments (time_parallel.hpp)
     // Automatic plan, adapted per handle: when most segments of a time-parallel block had to be
@@ -84,6 +84,7 @@ struct sdrgpu_pll {
     // sdrgpu_pll_set_phase_timing: events around the three kernels of a time-parallel block
     hipEvent_t phase_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool phase_on = false;
+    bool phase_recorded = false;  // the most recent block recorded all four
 
     bool adapt_serial() {
         if (tp.want_seg != 0) return false;
@@ -122,15 +123,24 @@ struct sdrgpu_pll {
         *seg = tp.seg(n, dp.nch, kMinSeg);
     }
 
+    // serial: the call's layout allows only the serial pass (alias_plan.hpp); such a block is
+    // serial anyway, so it takes nothing from the adapted plan's serial stretch.
     int make_spec(long n, PllSpec* sp, bool serial = false) {
         plan(n, &sp->seg, &sp->warm);
         tp.last_nseg = 0;
-        if (sp->seg > 0 && adapt_serial()) serial = true;
+        if (!serial && sp->seg > 0 && adapt_serial()) serial = true;
         if (serial) sp->seg = 0;
         if (sp->seg <= 0) return SDRGPU_OK;
         return tp.fill(*sp, n, dp.nch, kMinCk, stream.cur);
     }
-    hipEvent_t* phase() { return phase_on ? phase_ev : nullptr; }
+    // A planned block on device rows: the kernels, then the adapted plan's probe.
+    int run(const void* in, long ld_in, long n, float* out, uint8_t* locked, long ld_out, const PllSpec& sp) {
+        phase_recorded = phase_on && sp.seg > 0;
+        if (int st = pll_launch(dp, in, ld_in, n, out, locked, ld_out, d_state, sp, phase_on ? phase_ev : nullptr,
+                                stream.cur))
+            return st;
+        return probe(sp);
+    }
 
     void free_all() {
         DeviceGuard g(device);
@@ -148,6 +158,7 @@ struct sdrgpu_pll {
         stage_in.release();
         stage_out.release();
         stage_lock.release();
+        stage_alias.release();
         tp.buf.release();
         stream.destroy();
     }
@@ -242,7 +253,7 @@ int sdrgpu_pll_set_phase_timing(sdrgpu_pll* h, int on) {
 int sdrgpu_pll_last_phase_ms(sdrgpu_pll* h, float* pass1, float* rerun, float* walk) {
     if (!h || !pass1 || !rerun || !walk) return SDRGPU_ERR_INVALID;
     *pass1 = *rerun = *walk = 0.f;
-    if (!h->phase_on || h->tp.last_nseg <= 0) return SDRGPU_OK;
+    if (!h->phase_on || !h->phase_recorded) return SDRGPU_OK;
     DeviceGuard g(h->device);
     SDRGPU_HIP_TRY(hipStreamSynchronize(h->stream.cur));
     SDRGPU_HIP_TRY(hipEventElapsedTime(pass1, h->phase_ev[0], h->phase_ev[1]));
@@ -266,17 +277,19 @@ int sdrgpu_pll_process_dev(sdrgpu_pll* h, const void* d_in, size_t ld_in, size_t
     if (!d_in || !d_out || !d_locked || ld_in < n || ld_out < n) return SDRGPU_ERR_INVALID;
     DeviceGuard g(h->device);
     if (!g.ok()) return SDRGPU_ERR_DEVICE;
-    // an output range overlapping the input takes the serial pass (bytes_overlap, abi_common.hpp)
-    const size_t nch = (size_t)h->dp.nch, in_bytes = rows_span(nch, ld_in, n, h->dp.in_u8 ? 2 : sizeof(float2));
-    const bool alias = bytes_overlap(d_in, in_bytes, d_out, rows_span(nch, ld_out, n, sizeof(float))) ||
-                       bytes_overlap(d_in, in_bytes, d_locked, rows_span(nch, ld_out, n, 1));
-    PllSpec sp;
-    int st = h->make_spec((long)n, &sp, alias);
-    if (st) return st;
-    if ((st = pll_launch(h->dp, d_in, (long)ld_in, (long)n, d_out, d_locked, (long)ld_out, h->d_state, sp,
-                         h->phase(), h->stream.cur)))
+    // output or lock rows over the input rows (abi_common.hpp, alias_plan.hpp)
+    const size_t nch = (size_t)h->dp.nch, sb = h->dp.in_u8 ? 2 : sizeof(float2);
+    const alias::Rows in = alias_rows(d_in, ld_in, n, sb), out = alias_rows(d_out, ld_out, n, sizeof(float)),
+                      lock = alias_rows(d_locked, ld_out, n, 1);
+    if (alias::spans_overlap(nch, out, lock)) return SDRGPU_ERR_INVALID;
+    const alias::Plan ap = alias::stronger(alias::classify(nch, in, out), alias::classify(nch, in, lock));
+    int st;
+    if (ap == alias::Plan::copy_input &&
+        (st = stage_input(h->stage_alias, d_in, rows_span(nch, ld_in, n, sb), h->stream.cur)))
         return st;
-    return h->probe(sp);
+    PllSpec sp;
+    if ((st = h->make_spec((long)n, &sp, ap == alias::Plan::serial_in_place))) return st;
+    return h->run(d_in, (long)ld_in, (long)n, d_out, d_locked, (long)ld_out, sp);
 }
 
 int sdrgpu_pll_process(sdrgpu_pll* h, const void* in, size_t ld_in, size_t n, float* out,
@@ -297,9 +310,8 @@ int sdrgpu_pll_process(sdrgpu_pll* h, const void* in, size_t ld_in, size_t n, fl
     if ((st = h->make_spec((long)n, &sp))) return st;
     SDRGPU_HIP_TRY(hipMemcpy2DAsync(h->stage_in.ptr, n * sb, in, ld_in * sb, n * sb, nch,
                                     hipMemcpyHostToDevice, h->stream.cur));
-    if ((st = pll_launch(h->dp, h->stage_in.ptr, (long)n, (long)n,
-                         static_cast<float*>(h->stage_out.ptr), static_cast<uint8_t*>(h->stage_lock.ptr),
-                         (long)n, h->d_state, sp, h->phase(), h->stream.cur)) || (st = h->probe(sp)))
+    if ((st = h->run(h->stage_in.ptr, (long)n, (long)n, static_cast<float*>(h->stage_out.ptr),
+                     static_cast<uint8_t*>(h->stage_lock.ptr), (long)n, sp)))
         return st;
     SDRGPU_HIP_TRY(hipMemcpy2DAsync(out, ld_out * sizeof(float), h->stage_out.ptr, n * sizeof(float),
                                     n * sizeof(float), nch, hipMemcpyDeviceToHost, h->stream.cur));
@@ -327,9 +339,7 @@ int sdrgpu_pll_process_async(sdrgpu_pll* h, const void* in, size_t n, float* out
     uint8_t* d_lock = static_cast<uint8_t*>(h->async.out[slot][1].ptr);
     PllSpec sp;
     if ((st = h->make_spec((long)n, &sp))) return st;
-    if ((st = pll_launch(h->dp, h->stage_in.ptr, (long)n, (long)n, d_out, d_lock, (long)n,
-                         h->d_state, sp, h->phase(), h->stream.cur)) || (st = h->probe(sp)))
-        return st;
+    if ((st = h->run(h->stage_in.ptr, (long)n, (long)n, d_out, d_lock, (long)n, sp))) return st;
     void* const host[2] = {out, locked};
     return h->async.download(h->stream.cur, slot, host, ob, 2);
 }
