@@ -44,7 +44,7 @@ HBM_GBS = 8000.0
 
 def parse():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="all", choices=["c1", "c3", "c4", "c5", "c2u8", "c2host", "c2pinned", "src", "ex", "fm", "chan", "synth", "src_rows", "polyfir", "all"])
+    ap.add_argument("--config", default="all", choices=["c1", "c3", "c4", "c5", "c2u8", "c2host", "c2pinned", "src", "ex", "fm", "chan", "synth", "src_rows", "polyfir", "tuner", "all"])
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--c3-log2n", type=int, default=28)
@@ -980,6 +980,113 @@ def bench_polyfir(args):
         del x_dev, y_dev, f
     return lines
 
+# ------------------------------------------------------------------------------ tuner
+def tuner_theta(w, a):
+    """theta(a) = 2 pi ((w a) mod 2^32) / 2^32 in f64 from the wrapped integer phase (a < 2^32)."""
+    return 2.0 * np.pi * ((np.uint64(w) * np.asarray(a, np.uint64)) % np.uint64(1 << 32)).astype(np.float64) / 2.0 ** 32
+
+
+def tuner_taps(h, w):
+    """c[n] = h[n] exp(+j theta(n+1)): the complex taps of the chain form, as c64."""
+    return (h.astype(np.float64) * np.exp(1j * tuner_theta(w, np.arange(1, h.size + 1)))).astype(np.complex64)
+
+
+def tuner_spot_check(pyoracle, h, D, w, x, y, s0, nfr=2048):
+    """max |y - oracle| / rms over the frames whose windows lie in x[s0 - pre, s0 + nfr D): the
+    oracle's Fir(c, D) on that stretch (s0 and pre multiples of D, so the stretch keeps the
+    stream's decimation phase) times exp(-j theta((m+1) D)), without the frames its zero history
+    reaches."""
+    L = h.size
+    pre = min(s0, -(-L // D) * D)
+    ref = pyoracle.Fir(tuner_taps(h, w), D, sample_kind=1).process(x[s0 - pre:s0 + nfr * D])
+    m0 = (s0 - pre) // D
+    ref = ref * np.exp(-1j * tuner_theta(w, (np.arange(m0 + 1, m0 + 1 + ref.size) * D) % (1 << 32)))
+    skip = 0 if pre == s0 else -(-L // D)
+    got, ref = y[m0 + skip:m0 + ref.size], ref[skip:]
+    rms = float(np.sqrt(np.mean(np.abs(ref) ** 2)))
+    return float(np.max(np.abs(got.astype(np.complex128) - ref)) / rms)
+
+
+def bench_tuner(args):
+    """The tuner bank (sdrgpu_tuner_process_dev): one device-resident wideband stream into K
+    rows, hipEvents on the handle's stream around the whole call, state carried call to call.
+    Shapes (a)-(c) alternate with the form without the tuner, three repetitions each: K
+    sdrgpu_fir handles with the complex taps c_k and decim D over the same device buffer on one
+    stream (its rotation to baseband on the host is not counted).  (d) is the plain mixer,
+    against the 16 B/sample floor only.  The first call of every shape is checked against the
+    oracle on two stretches of two rows."""
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import pyoracle
+    import scipy.signal as ss
+    import sdrgpu
+    from sdrgpu.device import DeviceBuffer, synchronize
+    lines = []
+    for tag, K, D, L, log2n, u8 in (("a", 9, 8, 128, 26, False), ("b", 9, 8, 128, 26, True),
+                                    ("c", 64, 64, 1024, 24, False), ("d", 1, 1, 1, 26, False)):
+        n = 1 << log2n
+        h = (np.ones(1) if L == 1 else ss.firwin(L, 1.0 / max(D, 2))).astype(np.float32)
+        rng = np.random.default_rng(40 + K)
+        words = [int(v) for v in rng.integers(0, 1 << 32, K)]
+        if u8:
+            raw = np.tile(np.random.default_rng(41).integers(0, 256, 2 << 22, dtype=np.uint8), n >> 22)
+            x_dev = DeviceBuffer.from_numpy(raw)
+            xh = pyoracle.u8_to_c64(raw)
+            del raw
+        else:
+            xh = np.tile(cplx_pattern(1 << 22, 41), n >> 22)
+            x_dev = DeviceBuffer.from_numpy(xh)
+        n_out = n // D
+        y_dev = DeviceBuffer.empty(K * n_out)
+        kind = sdrgpu.CU8 if u8 else sdrgpu.C64
+        t = sdrgpu.Tuner(h, D, words=words, sample_kind=kind)
+        assert t.process_dev(x_dev.ptr, n, y_dev.ptr, n_out) == n_out
+        t.sync()
+        worst = 0.0
+        for k in sorted({0, K - 1}):
+            y = y_dev.download(n_out, offset_bytes=8 * k * n_out)
+            worst = max(worst, max(tuner_spot_check(pyoracle, h, D, words[k], xh, y, s0)
+                                   for s0 in (0, (n // 2) // D * D)))
+            del y
+        del xh
+        assert worst <= 1e-5 or args.no_check, worst
+
+        def step_tuner():
+            t.process_dev(x_dev.ptr, n, y_dev.ptr, n_out)
+
+        ms_tuner, ms_fir = [], []
+        if L > 1:
+            firs = [sdrgpu.filter.Fir(tuner_taps(h, w), decim=D, sample_kind=kind).design() for w in words]
+            for f in firs[1:]:
+                f.set_stream(firs[0].stream())
+            y_fir = DeviceBuffer.empty(K * n_out)
+
+            def step_fir():
+                for k, f in enumerate(firs):
+                    f.process_dev(x_dev.ptr, n, y_fir.ptr + 8 * k * n_out, n_out)
+        for _ in range(3):
+            ms_tuner.append(time_events(step_tuner, t.stream(), args.steps, args.warmup,
+                                        lambda: (t.sync(), synchronize()))[1])
+            if L > 1:
+                ms_fir.append(time_events(step_fir, firs[0].stream(), args.steps, args.warmup,
+                                          lambda: (firs[0].sync(), synchronize()))[1])
+        ms = float(np.mean(ms_tuner))
+        line = {"config": f"tuner ({tag}): {K} rows, decim {D}, {L} taps, 2^{log2n} "
+                          f"{'u8' if u8 else 'c64'} samples per call",
+                "metric": "input Msamples/s", "value": round(n / (ms * 1e-3) / 1e6, 1),
+                "tuner_ms": [round(v, 4) for v in ms_tuner],
+                "roofline": roof((2 if u8 else 8) + 8 * K / D, n, ms),
+                "products_per_input_sample": K * L / D, "outputs_per_row": n_out,
+                "spot_check_max_over_rms": worst}
+        if L > 1:
+            line["fir_handles_ms"] = [round(v, 4) for v in ms_fir]
+            line["fir_algorithm"] = firs[0].last_algorithm()
+            line["fir_kernel"] = firs[0].last_kernel()
+            line["tuner_slowest_over_fir_fastest"] = round(max(ms_tuner) / min(ms_fir), 3)
+            del firs, y_fir
+        lines.append(line)
+        del x_dev, y_dev, t
+    return lines
+
 
 def main():
     args = parse()
@@ -993,7 +1100,7 @@ def main():
         r = {"c1": bench_c1, "c3": bench_c3, "c4": bench_c4, "c5": bench_c5, "c2u8": bench_c2u8,
              "c2host": bench_c2host, "c2pinned": bench_c2pinned, "src": bench_src, "ex": bench_ex,
              "fm": bench_fm, "chan": bench_chan, "synth": bench_synth,
-             "src_rows": bench_src_rows, "polyfir": bench_polyfir}[c](args)
+             "src_rows": bench_src_rows, "polyfir": bench_polyfir, "tuner": bench_tuner}[c](args)
         for line in (r if isinstance(r, list) else [r]):
             if line is not None:
                 print(json.dumps(line), flush=True)

@@ -163,7 +163,7 @@ int sdrgpu_fir_process(sdrgpu_fir* h, const void* in, size_t n_in, void* out,
  * shifted): the handle then filters a device copy of the input, so the results are those of an
  * out-of-place call (the kernels store output tiles while other workgroups still read the
  * input under them).  The same holds for sdrgpu_firbank_process_dev, sdrgpu_chan_process_dev,
- * sdrgpu_synth_process_dev, sdrgpu_polyfir_process_dev, sdrgpu_fft_exec_dev,
+ * sdrgpu_synth_process_dev, sdrgpu_polyfir_process_dev, sdrgpu_tuner_process_dev, sdrgpu_fft_exec_dev,
  * sdrgpu_rfft_exec_dev and sdrgpu_stft_process_dev. */
 int sdrgpu_fir_process_dev(sdrgpu_fir* h, const void* d_in, size_t n_in, void* d_out,
                            size_t out_cap, size_t* n_out);
@@ -401,6 +401,71 @@ int sdrgpu_polyfir_sync(sdrgpu_polyfir* h);
 int sdrgpu_polyfir_reset(sdrgpu_polyfir* h);
 int sdrgpu_polyfir_clone(const sdrgpu_polyfir* h, sdrgpu_polyfir** out);
 void sdrgpu_polyfir_destroy(sdrgpu_polyfir* h);
+
+/* Tuner bank (digital down-converter): one wideband stream into nch rows, row k mixed down by its
+ * own frequency, low-passed with one shared real prototype and decimated by D = decim.
+ * Frequencies are 32-bit phase increments ("tuning words"), as in a hardware NCO: channel k has a
+ * word w_k, its frequency is w_k / 2^32 cycles per input sample (words at or above 2^31 are
+ * negative frequencies), and for an integer a
+ *   theta_k(a) = 2*pi * ((w_k * a) mod 2^32) / 2^32      (the product wraps in uint32),
+ * so the phase at any stream position is exact: never an accumulated float, nothing grows with
+ * the length of the stream.  With real f32 taps[0..ntaps), and t counted from the stream start
+ * across all calls:
+ *   y_k[m] = sum_{n<ntaps} taps[n] * x[t] * exp(-j*theta_k(t)),   t = m*D + D-1 - n,   x[<0] = 0
+ *          = exp(-j*theta_k((m+1)*D)) * sum_{n<ntaps} taps[n] * exp(+j*theta_k(n+1)) * x[t].
+ * The second line is the reference chain signal.filter(c_k).decimate(rate / D) (Fir with Complex
+ * taps, src/filter/fir.rs:23-32; Decimate keeps stream indices D-1, 2D-1, ...,
+ * src/signal/adapters/mod.rs:30-37) with c_k[n] = taps[n] * exp(+j*theta_k(n+1)), rotated to
+ * baseband.  It is sdrgpu_chan's definition with k/M replaced by w_k / 2^32: with
+ * w_k = k * 2^32 / M and D = M / os it is sdrgpu_chan's y_k[m] (within the parity tolerance).
+ * ntaps = 1, taps = {1}, D = 1 is a plain mixer.  n_out = floor((seen + n_in)/D) - floor(seen/D).
+ * The first line is what is computed (mix first: two real multiplies per tap product).
+ * Output layout, channel-major with ld_out, exactly as sdrgpu_chan_process[_dev] writes it: the
+ * layout sdrgpu_pll, sdrgpu_firbank, sdrgpu_biquad, sdrgpu_polyfir and the rows converter read.
+ * Partitions: any partition of the stream into calls -- 1-sample calls, empty calls and calls
+ * shorter than D included -- is bit-identical.  State is the last ntaps-1 RAW input samples (c64,
+ * after the u8 conversion) plus the sample count, kept on the device.
+ * Rows: row r of an nch-row handle is bit-identical to an nch = 1 handle created with word w_r: an
+ * output's summation order and its rotation factors depend on m and w only, not on nch, the call
+ * boundaries or the tiling (tiles are anchored to absolute frame indices).
+ * Retuning: sdrgpu_tuner_set_word(h, ch, w) takes effect at the next process call (it waits for
+ * the calls enqueued before it).  From then on channel ch gives, bit for bit, what a handle
+ * created with the new word and fed the same stream from its start gives: the history is raw
+ * samples, so there is no transient.  Other rows do not change.
+ * Non-finite samples: an inf or NaN sample makes non-finite exactly the outputs of every channel
+ * whose ntaps-sample window holds it; all other outputs are bit-identical to a clean run (a
+ * padding tap never multiplies a sample).  Values inside the affected outputs need not match the
+ * reference's (inf * cos may be NaN on either side).
+ * reset returns to the zero state and keeps the words; a clone keeps taps, words, count and
+ * history and gets its own stream.  d_out may overlap d_in (see sdrgpu_fir_process_dev).
+ * Kinds: samples SDRGPU_C64, or SDRGPU_CU8 with (v-128)/128 fused into the load; outputs are C64.
+ * Limits, checked before the device is looked at: a null pointer, ntaps, decim or nch of 0, or a
+ * kind outside the enum: SDRGPU_ERR_INVALID; decim > 2048, ntaps > 4096, nch > 4096 or SDRGPU_F32:
+ * SDRGPU_ERR_UNSUPPORTED.  ld_out < n_out: SDRGPU_ERR_OUTPUT_CAP with no state touched and *n_out
+ * set.  ch >= nch: SDRGPU_ERR_INVALID.  The handle holds a table of nch * (NF*D + ntaps-1) c64
+ * phase factors (NF frames per tile, 64..1024).
+ * sdrgpu_tuner_word (host only, no device): q = freq / rate (one double division),
+ * *word = nearbyint(ldexp(q - floor(q), 32)) mod 2^32, ties to even.  Non-finite arguments or
+ * rate <= 0: SDRGPU_ERR_INVALID. */
+typedef struct sdrgpu_tuner sdrgpu_tuner;
+
+int sdrgpu_tuner_word(double freq, double rate, uint32_t* word);
+int sdrgpu_tuner_create(int device, int sample_kind, const float* taps, size_t ntaps, uint32_t decim,
+                        const uint32_t* words, size_t nch, sdrgpu_tuner** out);
+int sdrgpu_tuner_set_word(sdrgpu_tuner* h, size_t ch, uint32_t word);
+int sdrgpu_tuner_get_word(const sdrgpu_tuner* h, size_t ch, uint32_t* word);
+int sdrgpu_tuner_get_decim(const sdrgpu_tuner* h, size_t* decim);
+int sdrgpu_tuner_set_stream(sdrgpu_tuner* h, void* hip_stream);
+int sdrgpu_tuner_get_stream(const sdrgpu_tuner* h, void** hip_stream);
+int sdrgpu_tuner_output_len(const sdrgpu_tuner* h, size_t n_in, size_t* n_out);
+int sdrgpu_tuner_process(sdrgpu_tuner* h, const void* in, size_t n_in, void* out, size_t ld_out,
+                         size_t* n_out);
+int sdrgpu_tuner_process_dev(sdrgpu_tuner* h, const void* d_in, size_t n_in, void* d_out,
+                             size_t ld_out, size_t* n_out);
+int sdrgpu_tuner_sync(sdrgpu_tuner* h);
+int sdrgpu_tuner_reset(sdrgpu_tuner* h);
+int sdrgpu_tuner_clone(const sdrgpu_tuner* h, sdrgpu_tuner** out);
+void sdrgpu_tuner_destroy(sdrgpu_tuner* h);
 
 /* =====================================================================================
  * FFT.

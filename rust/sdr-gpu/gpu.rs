@@ -524,6 +524,97 @@ impl<A> Drop for PolyFir<A> {
     }
 }
 
+// -------------------------------------------------------------------- tuner bank
+
+/// One wideband `Complex<f32>` stream into one row per tuning word (include/sdrgpu.h
+/// `sdrgpu_tuner`): row k is mixed down by `words[k] / 2^32` cycles per input sample (words at or
+/// above 2^31 are negative frequencies), low-passed with the real `taps` and decimated by
+/// `decim`.  It replaces `signal.filter(c_k).decimate(rate / decim)` with
+/// `c_k[n] = taps[n] * exp(j theta_k(n+1))` (fir.rs:23-32, adapters/mod.rs:30-37) and puts the
+/// station at baseband.  Phases are wrapped 32-bit products, exact at any stream position; a
+/// retuned row has no transient.
+pub struct GpuTuner {
+    h: *mut sys::sdrgpu_tuner,
+    nch: usize,
+}
+
+unsafe impl Send for GpuTuner {}
+
+impl GpuTuner {
+    /// The tuning word of `freq` Hz at `rate` samples per second (`sdrgpu_tuner_word`).
+    pub fn word(freq: f64, rate: f64) -> Result<u32> {
+        let mut w = 0;
+        check(unsafe { sys::sdrgpu_tuner_word(freq, rate, &mut w) })?;
+        Ok(w)
+    }
+
+    /// `decim`: 1..=2048; `taps.len()`: 1..=4096; `words.len()`: 1..=4096 rows.
+    pub fn new(taps: &[f32], decim: u32, words: &[u32]) -> Result<Self> {
+        let mut h = ptr::null_mut();
+        check(unsafe {
+            sys::sdrgpu_tuner_create(DEVICE, sys::SDRGPU_C64, taps.as_ptr(), taps.len(), decim,
+                                     words.as_ptr(), words.len(), &mut h)
+        })?;
+        Ok(GpuTuner { h, nch: words.len() })
+    }
+
+    /// Stations at `freqs` Hz from the centre of a stream at `rate` samples per second.
+    pub fn with_freqs(taps: &[f32], decim: u32, freqs: &[f64], rate: f64) -> Result<Self> {
+        let words = freqs.iter().map(|&f| Self::word(f, rate)).collect::<Result<Vec<u32>>>()?;
+        Self::new(taps, decim, &words)
+    }
+
+    /// Retunes row `ch` from the next `process` call on; the other rows do not change.
+    pub fn set_word(&mut self, ch: usize, word: u32) -> Result<()> {
+        check(unsafe { sys::sdrgpu_tuner_set_word(self.h, ch, word) })
+    }
+
+    pub fn word_of(&self, ch: usize) -> Result<u32> {
+        let mut w = 0;
+        check(unsafe { sys::sdrgpu_tuner_get_word(self.h, ch, &mut w) })?;
+        Ok(w)
+    }
+
+    pub fn decim(&self) -> usize {
+        let mut d = 0;
+        check(unsafe { sys::sdrgpu_tuner_get_decim(self.h, &mut d) }).expect("sdrgpu_tuner_get_decim");
+        d
+    }
+
+    /// One block of any length; `output` gets one row per word of the returned number of
+    /// samples (leading dimension = that number), the layout `GpuFirBank` and the PLL batch read.
+    pub fn process(&mut self, input: &[Complex<f32>], output: &mut Vec<Complex<f32>>) -> Result<usize> {
+        let mut m = 0;
+        check(unsafe { sys::sdrgpu_tuner_output_len(self.h, input.len(), &mut m) })?;
+        output.resize(self.nch * m.max(1), Complex::new(0.0, 0.0));
+        check(unsafe {
+            sys::sdrgpu_tuner_process(self.h, input.as_ptr() as *const _, input.len(),
+                                      output.as_mut_ptr() as *mut _, m.max(1), &mut m)
+        })?;
+        output.truncate(self.nch * m);
+        Ok(m)
+    }
+
+    pub fn reset(&mut self) -> Result<()> {
+        check(unsafe { sys::sdrgpu_tuner_reset(self.h) })
+    }
+}
+
+impl Clone for GpuTuner {
+    // the copy carries the taps, the words, the sample count and the history
+    fn clone(&self) -> Self {
+        let mut h = ptr::null_mut();
+        check(unsafe { sys::sdrgpu_tuner_clone(self.h, &mut h) }).expect("sdrgpu_tuner_clone");
+        GpuTuner { h, nch: self.nch }
+    }
+}
+
+impl Drop for GpuTuner {
+    fn drop(&mut self) {
+        unsafe { sys::sdrgpu_tuner_destroy(self.h) }
+    }
+}
+
 // ------------------------------------------------------------------ biquad designs
 
 /// The filter designs the PLL and the biquad stage take: `BiquadD` (src/filter/biquad.rs:

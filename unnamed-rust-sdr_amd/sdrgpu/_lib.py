@@ -180,6 +180,22 @@ SIGNATURES = [
     ("sdrgpu_polyfir_reset", c_int, [_H]),
     ("sdrgpu_polyfir_clone", c_int, [_H, _PH]),
     ("sdrgpu_polyfir_destroy", None, [_H]),
+    # tuner bank
+    ("sdrgpu_tuner_word", c_int, [ctypes.c_double, ctypes.c_double, POINTER(c_uint32)]),
+    ("sdrgpu_tuner_create", c_int,
+     [c_int, c_int, c_void_p, c_size_t, c_uint32, c_void_p, c_size_t, _PH]),
+    ("sdrgpu_tuner_set_word", c_int, [_H, c_size_t, c_uint32]),
+    ("sdrgpu_tuner_get_word", c_int, [_H, c_size_t, POINTER(c_uint32)]),
+    ("sdrgpu_tuner_get_decim", c_int, [_H, _PS]),
+    ("sdrgpu_tuner_set_stream", c_int, [_H, c_void_p]),
+    ("sdrgpu_tuner_get_stream", c_int, [_H, _PH]),
+    ("sdrgpu_tuner_output_len", c_int, [_H, c_size_t, _PS]),
+    ("sdrgpu_tuner_process", c_int, [_H, c_void_p, c_size_t, c_void_p, c_size_t, _PS]),
+    ("sdrgpu_tuner_process_dev", c_int, [_H, c_void_p, c_size_t, c_void_p, c_size_t, _PS]),
+    ("sdrgpu_tuner_sync", c_int, [_H]),
+    ("sdrgpu_tuner_reset", c_int, [_H]),
+    ("sdrgpu_tuner_clone", c_int, [_H, _PH]),
+    ("sdrgpu_tuner_destroy", None, [_H]),
     # FFT
     ("sdrgpu_fft_plan", c_int, [c_int, c_size_t, _PH]),
     ("sdrgpu_fft_set_stream", c_int, [_H, c_void_p]),

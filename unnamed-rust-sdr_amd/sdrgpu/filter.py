@@ -392,6 +392,145 @@ def polyfir_plan(up: int, down: int, consumed: int, n_in: int):
     return first.value, n.value
 
 
+# ---------------------------------------------------------------------------- Tuner
+def tuner_word(freq: float, rate: float) -> int:
+    """The 32-bit tuning word of `freq` at sample rate `rate` (sdrgpu_tuner_word; no device):
+    nearbyint(ldexp(q - floor(q), 32)) mod 2^32 with q = freq / rate, ties to even."""
+    w = ctypes.c_uint32()
+    check(lib().sdrgpu_tuner_word(float(freq), float(rate), ctypes.byref(w)), "sdrgpu_tuner_word")
+    return w.value
+
+
+class Tuner:
+    """Tuner bank (digital down-converter, sdrgpu_tuner): one wideband stream into K rows, row k
+    mixed down by its own frequency, low-passed with the shared real prototype `taps` and
+    decimated by `decim`.  Row k is the reference's `signal.filter(c_k).decimate(rate / decim)`
+    with c_k[n] = taps[n] * exp(+j*theta_k(n+1)) (fir.rs:23-32, adapters/mod.rs:30-37), times
+    exp(-j*theta_k((m+1)*decim)) for its m-th output since the stream start, which puts the
+    station at baseband; theta_k(a) = 2 pi ((w_k a) mod 2^32) / 2^32 for the 32-bit tuning word
+    w_k.  Give either `words`, or `freqs` in Hz with `rate` (through sdrgpu_tuner_word; negative
+    frequencies are words at or above 2^31).  sample_kind C64 or CU8 (rtl_tcp bytes); outputs are
+    C64, channel-major, the layout Pll, FirBank, Biquad, PolyFir and SampleRateRows read.  State
+    (the last len(taps)-1 raw samples, the sample count) carries across blocks; retuning a row
+    (set_word / set_freq) has no transient."""
+
+    def __init__(self, taps, decim: int, freqs=None, rate: Optional[float] = None, words=None,
+                 sample_kind: int = C64, device: int = 0, _handle=None):
+        taps = np.asarray(taps)
+        if np.iscomplexobj(taps) or taps.ndim != 1:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Tuner: taps must be a real 1-D array")
+        if (words is None) == (freqs is None):
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Tuner: give either words, or freqs with rate")
+        if words is None:
+            if rate is None:
+                raise _lib.SdrGpuError(_lib.ERR_INVALID, "Tuner: freqs need rate")
+            words = [tuner_word(f, rate) for f in np.atleast_1d(np.asarray(freqs, np.float64))]
+        w = np.atleast_1d(np.asarray(words))
+        if w.ndim != 1 or w.size and (np.any(w < 0) or np.any(w > 0xFFFFFFFF)):
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Tuner: words must be 32-bit, one per row")
+        self.taps = _as_c(taps, F32)
+        self.decim = int(decim)
+        self.rate = None if rate is None else float(rate)
+        self.sample_kind = sample_kind
+        self.device = device
+        self.nch = int(w.size)
+        self._h = ctypes.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            if not 0 <= self.decim < 1 << 32:
+                raise _lib.SdrGpuError(_lib.ERR_INVALID, "Tuner: decim out of range")
+            w32 = np.ascontiguousarray(w, dtype=np.uint32)
+            check(lib().sdrgpu_tuner_create(device, sample_kind, self.taps.ctypes.data,
+                                            self.taps.size, self.decim, w32.ctypes.data, w32.size,
+                                            ctypes.byref(self._h)), "sdrgpu_tuner_create")
+
+    def close(self):
+        if self._h:
+            lib().sdrgpu_tuner_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def words(self) -> np.ndarray:
+        """The current tuning words, one uint32 per row."""
+        out = np.empty(self.nch, np.uint32)
+        w = ctypes.c_uint32()
+        for k in range(self.nch):
+            check(lib().sdrgpu_tuner_get_word(self._h, k, ctypes.byref(w)), "sdrgpu_tuner_get_word")
+            out[k] = w.value
+        return out
+
+    @property
+    def freqs(self) -> np.ndarray:
+        """The realised frequencies word * rate / 2^32 in Hz, signed (words at or above 2^31 are
+        negative); in cycles per input sample when no rate was given."""
+        w = self.words.astype(np.int64)
+        w = np.where(w >= 1 << 31, w - (1 << 32), w)
+        return w * (1.0 if self.rate is None else self.rate) / 2.0 ** 32
+
+    def set_word(self, ch: int, word: int):
+        """Retune row ch from the next process call on; the other rows do not change."""
+        if not 0 <= int(word) <= 0xFFFFFFFF or ch < 0:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Tuner.set_word: out of range")
+        check(lib().sdrgpu_tuner_set_word(self._h, ch, int(word)), "sdrgpu_tuner_set_word")
+
+    def set_freq(self, ch: int, freq: float):
+        if self.rate is None:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Tuner.set_freq: the handle has no rate")
+        self.set_word(ch, tuner_word(freq, self.rate))
+
+    def clone(self) -> "Tuner":
+        h = ctypes.c_void_p()
+        check(lib().sdrgpu_tuner_clone(self._h, ctypes.byref(h)), "sdrgpu_tuner_clone")
+        return Tuner(self.taps, self.decim, rate=self.rate, words=self.words,
+                     sample_kind=self.sample_kind, device=self.device, _handle=h)
+
+    def reset(self):
+        check(lib().sdrgpu_tuner_reset(self._h), "sdrgpu_tuner_reset")
+
+    def set_stream(self, stream_ptr: Optional[int]):
+        check(lib().sdrgpu_tuner_set_stream(self._h, stream_ptr), "sdrgpu_tuner_set_stream")
+
+    def stream(self) -> int:
+        s = ctypes.c_void_p()
+        check(lib().sdrgpu_tuner_get_stream(self._h, ctypes.byref(s)), "sdrgpu_tuner_get_stream")
+        return s.value or 0
+
+    def output_len(self, n_in: int) -> int:
+        """Outputs per row the next process() call produces for n_in inputs."""
+        n = ctypes.c_size_t()
+        check(lib().sdrgpu_tuner_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
+        return n.value
+
+    def process(self, x) -> np.ndarray:
+        """x: (n,) host samples (CU8: 2n bytes or (n, 2)) -> (K, n_out) complex64."""
+        x = _as_c(x, self.sample_kind)
+        n_in = _nsamp(x.reshape(-1), self.sample_kind)
+        n_out = self.output_len(n_in)
+        out = np.empty((self.nch, max(n_out, 1)), dtype=np.complex64)
+        got = ctypes.c_size_t()
+        check(lib().sdrgpu_tuner_process(self._h, x.ctypes.data, n_in, out.ctypes.data,
+                                         out.shape[1], ctypes.byref(got)), "sdrgpu_tuner_process")
+        return out[:, :got.value]
+
+    def process_dev(self, d_in_ptr: int, n_in: int, d_out_ptr: int, ld_out: int) -> int:
+        """Enqueue on the handle's stream with device pointers; row k's outputs go to
+        d_out + k*ld_out samples.  Returns n_out (per row)."""
+        got = ctypes.c_size_t()
+        check(lib().sdrgpu_tuner_process_dev(self._h, d_in_ptr, n_in, d_out_ptr, ld_out,
+                                             ctypes.byref(got)), "sdrgpu_tuner_process_dev")
+        return got.value
+
+    def sync(self):
+        check(lib().sdrgpu_tuner_sync(self._h), "sdrgpu_tuner_sync")
+
+
 # ---------------------------------------------------------------------- Channelizer
 class Channelizer:
     """Polyphase channelizer: one wideband stream into nch channel rows.  Channel k is the

@@ -135,7 +135,6 @@ def receivers(wideband, nch: int, taps, oversample: int = 2, rate_taps=None):
     caller's taps: PolyFir(h1, up1, down1, nch) with up1/down1 the exact fraction
     144000 / row rate (ERR_UNSUPPORTED where there is none within the PolyFir's limits), and
     PolyFir(h2, 1, 3, 2 nch).  The default None leaves the chain above as it is."""
-    from .signal import Signal
     if wideband.sample_kind not in (_lib.C64, _lib.CU8):
         raise _lib.SdrGpuError(_lib.ERR_INVALID, "fm.receivers: expects a c64 or CU8 Signal")
     kind = wideband.sample_kind
@@ -143,6 +142,44 @@ def receivers(wideband, nch: int, taps, oversample: int = 2, rate_taps=None):
     probe = _filter.Channelizer(taps, nch, sample_kind=kind, oversample=oversample)
     row_rate = wideband.rate() / probe.decim
     probe.close()
+
+    def rows():
+        chan = _filter.Channelizer(taps, nch, sample_kind=kind, oversample=oversample)
+        for b in wideband.blocks():
+            yield chan.process(b)
+
+    return _stations(rows, nch, row_rate, rate_taps)
+
+
+def tuned_receivers(wideband, freqs, decim: int, taps, rate_taps=None):
+    """`receivers`' chain with a Tuner in the Channelizer's place: station k is the one `freqs[k]`
+    Hz from the capture's centre, anywhere in the band -- no uniform grid.  `wideband` (c64 or
+    rtl_tcp CU8 Signal) -> Signal of (len(freqs), n, 2) f32 blocks, (left, right) at 48 kHz:
+
+      Tuner(taps, decim, freqs, rate)                 -> (K, n) c64 at rate / decim
+
+    and then every stage of `receivers` on the rows; rate_taps as there."""
+    if wideband.sample_kind not in (_lib.C64, _lib.CU8):
+        raise _lib.SdrGpuError(_lib.ERR_INVALID, "fm.tuned_receivers: expects a c64 or CU8 Signal")
+    kind = wideband.sample_kind
+    taps = np.asarray(taps, np.float32)
+    freqs = [float(f) for f in np.atleast_1d(np.asarray(freqs, np.float64))]
+    if not freqs or int(decim) < 1:
+        raise _lib.SdrGpuError(_lib.ERR_INVALID, "fm.tuned_receivers: needs stations and decim >= 1")
+    rate = wideband.rate()
+
+    def rows():
+        tuner = _filter.Tuner(taps, decim, freqs=freqs, rate=rate, sample_kind=kind)
+        for b in wideband.blocks():
+            yield tuner.process(b)
+
+    return _stations(rows, len(freqs), rate / int(decim), rate_taps)
+
+
+def _stations(front, nch: int, row_rate: float, rate_taps):
+    """What follows the front end in `receivers` and `tuned_receivers`: `front()` yields
+    (nch, n) c64 blocks of station rows at row_rate."""
+    from .signal import Signal
     dev = np.float32(DEVIATION)
     r1 = float(np.float32(48000.0 * 3.0)) / float(np.float32(row_rate))
     r2 = float(np.float32(48000.0)) / float(np.float32(48000.0 * 3.0))
@@ -161,10 +198,10 @@ def receivers(wideband, nch: int, taps, oversample: int = 2, rate_taps=None):
         return _convert_rows(_resample.SampleRateRows(_resample.ConverterType.SincBestQuality, 2 * nch), r2, rows)
 
     def fm():
-        chan = _filter.Channelizer(taps, nch, sample_kind=kind, oversample=oversample)
-        disc = discriminator_design().design(row_rate, nch=nch)
-        for b in wideband.blocks():
-            rows = chan.process(b)
+        disc = None
+        for rows in front():
+            if disc is None:
+                disc = discriminator_design().design(row_rate, nch=nch)
             if rows.shape[1]:
                 v, locked = disc.process(rows)
                 yield np.where(locked != 0, v, np.float32(0.0)).astype(np.float32) / dev

@@ -162,6 +162,26 @@ class Signal:
                     yield y
         return Signal(self._rate * up / down, gen, sk)
 
+    def tune(self, freq: float, decim: int, taps) -> "Signal":
+        """One station of a wideband c64 or CU8 Signal (filter.Tuner with one row): mixed down by
+        `freq` Hz (rounded to a 32-bit tuning word of this Signal's rate), low-passed with the
+        real `taps`, every `decim`-th sample kept; a c64 Signal at rate / decim.  It is
+        .filter(taps * exp(+j*theta(n+1))).decimate(rate / decim) rotated to baseband."""
+        sk = self.sample_kind
+        if sk == _lib.F32:
+            raise _lib.SdrGpuError(_lib.ERR_UNSUPPORTED, "tune: F32 samples")
+        src = self
+        word = _filter.tuner_word(freq, self._rate)
+
+        def gen():
+            t = _filter.Tuner(taps, decim, words=[word], rate=src._rate,
+                              sample_kind=_lib.CU8 if sk == _lib.CU8 else _lib.C64)
+            for b in src.blocks():
+                y = t.process(b)[0]
+                if y.size:
+                    yield y
+        return Signal(self._rate / decim, gen, _lib.C64)
+
     def resample(self, rate: float) -> "Signal":
         """Signal::resample (src/signal/mod.rs:78-84): SincBestQuality (this library's own
         sinc table)."""
