@@ -44,7 +44,7 @@ HBM_GBS = 8000.0
 
 def parse():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="all", choices=["c1", "c3", "c4", "c5", "c2u8", "c2host", "c2pinned", "src", "ex", "fm", "chan", "synth", "src_rows", "polyfir", "tuner", "all"])
+    ap.add_argument("--config", default="all", choices=["c1", "c3", "c4", "c5", "c2u8", "c2host", "c2pinned", "src", "ex", "fm", "chan", "synth", "src_rows", "polyfir", "tuner", "upconv", "all"])
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--c3-log2n", type=int, default=28)
@@ -1088,6 +1088,87 @@ def bench_tuner(args):
     return lines
 
 
+# ------------------------------------------------------------------------------ upconv
+def upconv_spot_check(h, I, words, rows, y, q0, nfr):
+    """max |y - f64| / rms over the outputs of frames [q0, q0 + nfr): zero-stuffing plus
+    convolution per row in f64 on the frames that reach them, mixed from integer phases, summed."""
+    P = -(-h.size // I)
+    pre = min(q0, P)
+    t = np.arange(q0 * I, (q0 + nfr) * I, dtype=np.uint64) % np.uint64(1 << 32)
+    ref = np.zeros(nfr * I, np.complex128)
+    for w, x in zip(words, rows):
+        u = np.zeros((pre + nfr) * I, np.complex128)
+        u[::I] = x[q0 - pre:q0 + nfr]
+        v = np.convolve(u, h.astype(np.float64))[pre * I:(pre + nfr) * I]
+        ref += np.exp(1j * tuner_theta(w, t)) * v
+    got = y[q0 * I:(q0 + nfr) * I].astype(np.complex128)
+    return float(np.max(np.abs(got - ref)) / np.sqrt(np.mean(np.abs(ref) ** 2)))
+
+
+def bench_upconv(args):
+    """The up-converter bank (sdrgpu_upconv_process_dev): K device-resident rows onto their
+    frequencies of one wideband stream, hipEvents on the handle's stream around the whole call,
+    state carried call to call.  Shapes (a) and (b) alternate, three repetitions each, with the
+    nearest route without the bank: the PolyFir(h, I, 1, nch=K) rows call alone, which writes K
+    times the samples and still lacks the mix and the sum over rows, so it is a lower bound on
+    that route.  (c) is the plain up-mixer, against the 16 B/sample floor only.  The first call of
+    every shape is checked against f64 on two stretches."""
+    import scipy.signal as ss
+    import sdrgpu
+    from sdrgpu.device import DeviceBuffer, synchronize
+    lines = []
+    for tag, K, I, L, log2f in (("a", 9, 8, 128, 23), ("b", 64, 64, 1024, 18), ("c", 1, 1, 1, 26)):
+        n = 1 << log2f
+        n_out = n * I
+        h = ((np.ones(1) if L == 1 else ss.firwin(L, 1.0 / max(I, 2))) * I).astype(np.float32)
+        rng = np.random.default_rng(50 + K)
+        words = [int(v) for v in rng.integers(0, 1 << 32, K)]
+        base = cplx_pattern(min(n, 1 << 20), 51)
+        rows = np.stack([np.tile(np.roll(base, 1009 * k), n // base.size) for k in range(K)])
+        x_dev = DeviceBuffer.from_numpy(rows)
+        y_dev = DeviceBuffer.empty(n_out)
+        u = sdrgpu.Upconverter(h, I, words=words)
+        assert u.process_dev(x_dev.ptr, n, n, y_dev.ptr, n_out) == n_out
+        u.sync()
+        y = y_dev.download(n_out)
+        nfr = max(4096 // I, 8)
+        worst = max(upconv_spot_check(h, I, words, rows, y, q0, nfr) for q0 in (0, n // 2 + 3))
+        del y, rows
+        assert worst <= 1e-5 or args.no_check, worst
+
+        def step_upconv():
+            u.process_dev(x_dev.ptr, n, n, y_dev.ptr, n_out)
+
+        ms_up, ms_pf = [], []
+        if L > 1:
+            pf = sdrgpu.PolyFir(h, I, 1, nch=K)
+            y_pf = DeviceBuffer.empty(K * n_out)
+
+            def step_polyfir():
+                pf.process_dev(x_dev.ptr, n, n, y_pf.ptr, n_out)
+        for _ in range(3):
+            ms_up.append(time_events(step_upconv, u.stream(), args.steps, args.warmup,
+                                     lambda: (u.sync(), synchronize()))[1])
+            if L > 1:
+                ms_pf.append(time_events(step_polyfir, pf.stream(), args.steps, args.warmup,
+                                         lambda: (pf.sync(), synchronize()))[1])
+        ms = float(np.mean(ms_up))
+        line = {"config": f"upconv ({tag}): {K} rows, interp {I}, {L} taps, 2^{log2f} frames per row "
+                          f"and call",
+                "metric": "output Msamples/s", "value": round(n_out / (ms * 1e-3) / 1e6, 1),
+                "upconv_ms": [round(v, 4) for v in ms_up],
+                "roofline": roof(8 * (1 + K / I), n_out, ms),
+                "products_per_output": K * -(-L // I), "outputs": n_out,
+                "spot_check_max_over_rms": worst}
+        if L > 1:
+            line["polyfir_rows_ms"] = [round(v, 4) for v in ms_pf]
+            line["upconv_slowest_over_polyfir_fastest"] = round(max(ms_up) / min(ms_pf), 3)
+            del pf, y_pf
+        lines.append(line)
+        del x_dev, y_dev, u
+    return lines
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1100,7 +1181,8 @@ def main():
         r = {"c1": bench_c1, "c3": bench_c3, "c4": bench_c4, "c5": bench_c5, "c2u8": bench_c2u8,
              "c2host": bench_c2host, "c2pinned": bench_c2pinned, "src": bench_src, "ex": bench_ex,
              "fm": bench_fm, "chan": bench_chan, "synth": bench_synth,
-             "src_rows": bench_src_rows, "polyfir": bench_polyfir, "tuner": bench_tuner}[c](args)
+             "src_rows": bench_src_rows, "polyfir": bench_polyfir, "tuner": bench_tuner,
+             "upconv": bench_upconv}[c](args)
         for line in (r if isinstance(r, list) else [r]):
             if line is not None:
                 print(json.dumps(line), flush=True)

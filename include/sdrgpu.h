@@ -467,6 +467,70 @@ int sdrgpu_tuner_reset(sdrgpu_tuner* h);
 int sdrgpu_tuner_clone(const sdrgpu_tuner* h, sdrgpu_tuner** out);
 void sdrgpu_tuner_destroy(sdrgpu_tuner* h);
 
+/* Up-converter bank (digital up-converter): nch rows of c64 frames onto any frequencies of one
+ * wideband stream: the tuner bank, transposed, and the way back from its rows.  Row k is
+ * interpolated by I = interp with one shared real prototype taps[0..L), mixed up by its tuning
+ * word w_k (sdrgpu_tuner_word(freq, rate) with rate the wideband, output rate) and the rows are
+ * summed.  With theta_k(a) = 2*pi * ((w_k * a) mod 2^32) / 2^32 exactly as in sdrgpu_tuner, and
+ * frames q and outputs t counted from the stream start across all calls:
+ *   v_k[t] = sum_{j >= 0, p + I*j < L} taps[p + I*j] * x_k[q - j],   p = t mod I, q = t div I, x_k[<0] = 0
+ *   s[t]   = sum_{k = 0 .. nch-1, in this order} exp(+j*theta_k(t)) * v_k[t].
+ * v_k is sdrgpu_polyfir's definition with up = I, down = 1: zero-stuffing by I followed by the
+ * reference's real-tap Fir (src/filter/fir.rs:23-32).  Only non-zero products are formed; a phase
+ * with no tap (L < I) gives exact zeros.  No gain is applied: the caller scales the taps by I.
+ * After n frames per row exactly n*I outputs exist: no latency, no flush.  interp = 1,
+ * taps = {1}, nch = 1 is a plain up-mixer.  The sum over rows is formed in one pass in row order,
+ * without atomics and without a split over rows, so its order never depends on the launch.
+ * Round trip: the tuner mixes with exp(-j*theta_k(t)) at the same absolute t, so the carriers
+ * cancel exactly.  A sdrgpu_tuner with taps h_a, decim = I and the same words, applied to this
+ * handle's output made with taps h_s, returns row k filtered by the cascade of h_s and h_a (plus
+ * what leaks in from the other rows), delayed by d = (len(h_a) + len(h_s) - 2*I) / (2*I) frames
+ * whenever that is a whole number.
+ * Layout: rows as in sdrgpu_firbank and as sdrgpu_tuner writes them: row k starts at
+ * in + k*ld_in (frames); the output is one stream of n_in*I samples.
+ * Properties, held by construction (tiles are anchored to absolute output indices and the tile
+ * size is chosen from interp and ntaps alone; an output's factors and summation order depend on t
+ * and the words only):
+ *   Partitions: any partition of the frames into calls, 1-frame and empty calls included, is
+ *   bit-identical.
+ *   Rows: an nch-row handle whose rows other than r are all zero gives the output of an nch = 1
+ *   handle with word w_r fed row r (equal as numbers: a zero row adds exact zeros).
+ *   Retuning: sdrgpu_upconv_set_word(h, ch, w) takes effect at the next process call (it waits
+ *   for the calls enqueued before it).  From then on the output equals, bit for bit, what a
+ *   handle created with the new word and fed the same rows from the start gives: the history is
+ *   raw frames, so there is no transient.
+ *   Non-finite samples: a non-finite x_k[q] makes non-finite exactly the outputs t with
+ *   0 <= t - q*I < L; all others are bit-identical to a clean run.
+ *   reset returns to the zero state and keeps the words; a clone keeps taps, words, count and
+ *   history and gets its own stream.  d_out may overlap d_in (see sdrgpu_fir_process_dev).
+ * State, on the device: the last ceil(L/I) - 1 frames per row, and the frame count.
+ * Kinds: rows are SDRGPU_C64 and so is the output.
+ * Limits, checked before the device is looked at: a null pointer, ntaps, interp or nch of 0, or a
+ * kind outside the enum: SDRGPU_ERR_INVALID; interp > 2048, ntaps > 4096, ceil(ntaps/interp) >
+ * 1024, nch > 4096, or SDRGPU_F32 / SDRGPU_CU8 rows: SDRGPU_ERR_UNSUPPORTED.  ld_in < n_in:
+ * SDRGPU_ERR_INVALID.  n_in*I > cap_out: SDRGPU_ERR_OUTPUT_CAP with no state touched and *n_out
+ * set.  ch >= nch: SDRGPU_ERR_INVALID.  The handle holds a table of nch * NO c64 phase factors,
+ * NO the outputs per tile: 8 * floor(256/I) * I for I <= 256 (1800 .. 2048), else I (DESIGN.md
+ * 3.10). */
+typedef struct sdrgpu_upconv sdrgpu_upconv;
+
+int sdrgpu_upconv_create(int device, int sample_kind, const float* taps, size_t ntaps, uint32_t interp,
+                         const uint32_t* words, size_t nch, sdrgpu_upconv** out);
+int sdrgpu_upconv_set_word(sdrgpu_upconv* h, size_t ch, uint32_t word);
+int sdrgpu_upconv_get_word(const sdrgpu_upconv* h, size_t ch, uint32_t* word);
+int sdrgpu_upconv_get_interp(const sdrgpu_upconv* h, size_t* interp);
+int sdrgpu_upconv_set_stream(sdrgpu_upconv* h, void* hip_stream);
+int sdrgpu_upconv_get_stream(const sdrgpu_upconv* h, void** hip_stream);
+int sdrgpu_upconv_output_len(const sdrgpu_upconv* h, size_t n_in, size_t* n_out);  /* n_in * I */
+int sdrgpu_upconv_process(sdrgpu_upconv* h, const void* in, size_t ld_in, size_t n_in, void* out,
+                          size_t cap_out, size_t* n_out);
+int sdrgpu_upconv_process_dev(sdrgpu_upconv* h, const void* d_in, size_t ld_in, size_t n_in,
+                              void* d_out, size_t cap_out, size_t* n_out);
+int sdrgpu_upconv_sync(sdrgpu_upconv* h);
+int sdrgpu_upconv_reset(sdrgpu_upconv* h);
+int sdrgpu_upconv_clone(const sdrgpu_upconv* h, sdrgpu_upconv** out);
+void sdrgpu_upconv_destroy(sdrgpu_upconv* h);
+
 /* =====================================================================================
  * FFT.
  * Replaces: fft::fft  (src/fft.rs:3-28)  -- forward DFT, fftshift collate, x 1/sqrt(N)

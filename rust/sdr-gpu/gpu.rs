@@ -615,6 +615,93 @@ impl Drop for GpuTuner {
     }
 }
 
+// -------------------------------------------------------------- up-converter bank
+
+/// One row of `Complex<f32>` frames per tuning word onto one wideband stream (include/sdrgpu.h
+/// `sdrgpu_upconv`), the way back from `GpuTuner`: row k is zero-stuffed by `interp`, filtered
+/// with the real `taps` (fir.rs:23-32), mixed up by `words[k] / 2^32` cycles per output sample
+/// and the rows are summed in row order.  `n` frames per row give exactly `n * interp` samples,
+/// unscaled (scale the taps by `interp`).  Phases are wrapped 32-bit products at the tuner's
+/// absolute sample index, so a `GpuTuner` with the same words cancels the carriers exactly.
+pub struct GpuUpconverter {
+    h: *mut sys::sdrgpu_upconv,
+    nch: usize,
+}
+
+unsafe impl Send for GpuUpconverter {}
+
+impl GpuUpconverter {
+    /// `interp`: 1..=2048; `taps.len()`: 1..=4096 and at most `1024 * interp`; `words.len()`:
+    /// 1..=4096 rows.  Words come from `GpuTuner::word(freq, rate)` with the wideband rate.
+    pub fn new(taps: &[f32], interp: u32, words: &[u32]) -> Result<Self> {
+        let mut h = ptr::null_mut();
+        check(unsafe {
+            sys::sdrgpu_upconv_create(DEVICE, sys::SDRGPU_C64, taps.as_ptr(), taps.len(), interp,
+                                      words.as_ptr(), words.len(), &mut h)
+        })?;
+        Ok(GpuUpconverter { h, nch: words.len() })
+    }
+
+    /// Rows onto `freqs` Hz from the centre of a stream at `rate` samples per second.
+    pub fn with_freqs(taps: &[f32], interp: u32, freqs: &[f64], rate: f64) -> Result<Self> {
+        let words = freqs.iter().map(|&f| GpuTuner::word(f, rate)).collect::<Result<Vec<u32>>>()?;
+        Self::new(taps, interp, &words)
+    }
+
+    /// Retunes row `ch` from the next `process` call on.
+    pub fn set_word(&mut self, ch: usize, word: u32) -> Result<()> {
+        check(unsafe { sys::sdrgpu_upconv_set_word(self.h, ch, word) })
+    }
+
+    pub fn word_of(&self, ch: usize) -> Result<u32> {
+        let mut w = 0;
+        check(unsafe { sys::sdrgpu_upconv_get_word(self.h, ch, &mut w) })?;
+        Ok(w)
+    }
+
+    pub fn interp(&self) -> usize {
+        let mut d = 0;
+        check(unsafe { sys::sdrgpu_upconv_get_interp(self.h, &mut d) }).expect("sdrgpu_upconv_get_interp");
+        d
+    }
+
+    /// `rows`: one row per word, `frames` frames each, row k at `rows[k * frames..]` (the layout
+    /// `GpuTuner::process` writes).  `output` gets the `frames * interp` samples; returns that number.
+    pub fn process(&mut self, rows: &[Complex<f32>], frames: usize, output: &mut Vec<Complex<f32>>) -> Result<usize> {
+        if rows.len() != self.nch * frames {
+            return Err(Error(sys::SDRGPU_ERR_INVALID));
+        }
+        let mut m = 0;
+        check(unsafe { sys::sdrgpu_upconv_output_len(self.h, frames, &mut m) })?;
+        output.resize(m.max(1), Complex::new(0.0, 0.0));
+        check(unsafe {
+            sys::sdrgpu_upconv_process(self.h, rows.as_ptr() as *const _, frames.max(1), frames,
+                                       output.as_mut_ptr() as *mut _, m.max(1), &mut m)
+        })?;
+        output.truncate(m);
+        Ok(m)
+    }
+
+    pub fn reset(&mut self) -> Result<()> {
+        check(unsafe { sys::sdrgpu_upconv_reset(self.h) })
+    }
+}
+
+impl Clone for GpuUpconverter {
+    // the copy carries the taps, the words, the frame count and the history
+    fn clone(&self) -> Self {
+        let mut h = ptr::null_mut();
+        check(unsafe { sys::sdrgpu_upconv_clone(self.h, &mut h) }).expect("sdrgpu_upconv_clone");
+        GpuUpconverter { h, nch: self.nch }
+    }
+}
+
+impl Drop for GpuUpconverter {
+    fn drop(&mut self) {
+        unsafe { sys::sdrgpu_upconv_destroy(self.h) }
+    }
+}
+
 // ------------------------------------------------------------------ biquad designs
 
 /// The filter designs the PLL and the biquad stage take: `BiquadD` (src/filter/biquad.rs:

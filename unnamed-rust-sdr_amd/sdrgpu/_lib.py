@@ -196,6 +196,23 @@ SIGNATURES = [
     ("sdrgpu_tuner_reset", c_int, [_H]),
     ("sdrgpu_tuner_clone", c_int, [_H, _PH]),
     ("sdrgpu_tuner_destroy", None, [_H]),
+    # up-converter bank
+    ("sdrgpu_upconv_create", c_int,
+     [c_int, c_int, c_void_p, c_size_t, c_uint32, c_void_p, c_size_t, _PH]),
+    ("sdrgpu_upconv_set_word", c_int, [_H, c_size_t, c_uint32]),
+    ("sdrgpu_upconv_get_word", c_int, [_H, c_size_t, POINTER(c_uint32)]),
+    ("sdrgpu_upconv_get_interp", c_int, [_H, _PS]),
+    ("sdrgpu_upconv_set_stream", c_int, [_H, c_void_p]),
+    ("sdrgpu_upconv_get_stream", c_int, [_H, _PH]),
+    ("sdrgpu_upconv_output_len", c_int, [_H, c_size_t, _PS]),
+    ("sdrgpu_upconv_process", c_int,
+     [_H, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, _PS]),
+    ("sdrgpu_upconv_process_dev", c_int,
+     [_H, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, _PS]),
+    ("sdrgpu_upconv_sync", c_int, [_H]),
+    ("sdrgpu_upconv_reset", c_int, [_H]),
+    ("sdrgpu_upconv_clone", c_int, [_H, _PH]),
+    ("sdrgpu_upconv_destroy", None, [_H]),
     # FFT
     ("sdrgpu_fft_plan", c_int, [c_int, c_size_t, _PH]),
     ("sdrgpu_fft_set_stream", c_int, [_H, c_void_p]),

@@ -530,6 +530,143 @@ class Tuner:
     def sync(self):
         check(lib().sdrgpu_tuner_sync(self._h), "sdrgpu_tuner_sync")
 
+    def upconverter(self, taps) -> "Upconverter":
+        """The up-converter bank of this tuner's words, interp = decim, rate and device with the
+        prototype `taps`: the way back from its rows."""
+        return Upconverter(taps, self.decim, rate=self.rate, words=self.words, device=self.device)
+
+
+# ---------------------------------------------------------------------------- Upconverter
+class Upconverter:
+    """Up-converter bank (digital up-converter, sdrgpu_upconv): K rows of c64 frames onto any
+    frequencies of one wideband stream, the way back from Tuner.  Row k is zero-stuffed by
+    `interp` and filtered with the shared real prototype `taps` (PolyFir(taps, interp, 1);
+    fir.rs:23-32), multiplied by exp(+j*theta_k(t)) for its t-th output since the stream start,
+    theta_k(a) = 2 pi ((w_k a) mod 2^32) / 2^32, and the rows are summed in row order: n frames
+    per row give exactly n*interp samples, unscaled (scale the taps by interp).  Give either
+    `words`, or `freqs` in Hz with `rate`, the wideband (output) rate.  State (the last
+    ceil(len(taps)/interp)-1 frames per row, the frame count) carries across blocks; retuning a
+    row (set_word / set_freq) has no transient."""
+
+    def __init__(self, taps, interp: int, freqs=None, rate: Optional[float] = None, words=None,
+                 device: int = 0, _handle=None):
+        taps = np.asarray(taps)
+        if np.iscomplexobj(taps) or taps.ndim != 1:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Upconverter: taps must be a real 1-D array")
+        if (words is None) == (freqs is None):
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Upconverter: give either words, or freqs with rate")
+        if words is None:
+            if rate is None:
+                raise _lib.SdrGpuError(_lib.ERR_INVALID, "Upconverter: freqs need rate")
+            words = [tuner_word(f, rate) for f in np.atleast_1d(np.asarray(freqs, np.float64))]
+        w = np.atleast_1d(np.asarray(words))
+        if w.ndim != 1 or w.size and (np.any(w < 0) or np.any(w > 0xFFFFFFFF)):
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Upconverter: words must be 32-bit, one per row")
+        self.taps = _as_c(taps, F32)
+        self.interp = int(interp)
+        self.rate = None if rate is None else float(rate)
+        self.sample_kind = C64
+        self.device = device
+        self.nch = int(w.size)
+        self._h = ctypes.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            if not 0 <= self.interp < 1 << 32:
+                raise _lib.SdrGpuError(_lib.ERR_INVALID, "Upconverter: interp out of range")
+            w32 = np.ascontiguousarray(w, dtype=np.uint32)
+            check(lib().sdrgpu_upconv_create(device, C64, self.taps.ctypes.data, self.taps.size,
+                                             self.interp, w32.ctypes.data, w32.size,
+                                             ctypes.byref(self._h)), "sdrgpu_upconv_create")
+
+    def close(self):
+        if self._h:
+            lib().sdrgpu_upconv_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def words(self) -> np.ndarray:
+        """The current tuning words, one uint32 per row."""
+        out = np.empty(self.nch, np.uint32)
+        w = ctypes.c_uint32()
+        for k in range(self.nch):
+            check(lib().sdrgpu_upconv_get_word(self._h, k, ctypes.byref(w)), "sdrgpu_upconv_get_word")
+            out[k] = w.value
+        return out
+
+    @property
+    def freqs(self) -> np.ndarray:
+        """The realised frequencies word * rate / 2^32 in Hz, signed (words at or above 2^31 are
+        negative); in cycles per output sample when no rate was given."""
+        w = self.words.astype(np.int64)
+        w = np.where(w >= 1 << 31, w - (1 << 32), w)
+        return w * (1.0 if self.rate is None else self.rate) / 2.0 ** 32
+
+    def set_word(self, ch: int, word: int):
+        """Retune row ch from the next process call on."""
+        if not 0 <= int(word) <= 0xFFFFFFFF or ch < 0:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Upconverter.set_word: out of range")
+        check(lib().sdrgpu_upconv_set_word(self._h, ch, int(word)), "sdrgpu_upconv_set_word")
+
+    def set_freq(self, ch: int, freq: float):
+        if self.rate is None:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Upconverter.set_freq: the handle has no rate")
+        self.set_word(ch, tuner_word(freq, self.rate))
+
+    def clone(self) -> "Upconverter":
+        h = ctypes.c_void_p()
+        check(lib().sdrgpu_upconv_clone(self._h, ctypes.byref(h)), "sdrgpu_upconv_clone")
+        return Upconverter(self.taps, self.interp, rate=self.rate, words=self.words,
+                           device=self.device, _handle=h)
+
+    def reset(self):
+        check(lib().sdrgpu_upconv_reset(self._h), "sdrgpu_upconv_reset")
+
+    def set_stream(self, stream_ptr: Optional[int]):
+        check(lib().sdrgpu_upconv_set_stream(self._h, stream_ptr), "sdrgpu_upconv_set_stream")
+
+    def stream(self) -> int:
+        s = ctypes.c_void_p()
+        check(lib().sdrgpu_upconv_get_stream(self._h, ctypes.byref(s)), "sdrgpu_upconv_get_stream")
+        return s.value or 0
+
+    def output_len(self, n_in: int) -> int:
+        """Samples the next process() call produces for n_in frames per row."""
+        n = ctypes.c_size_t()
+        check(lib().sdrgpu_upconv_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
+        return n.value
+
+    def process(self, rows) -> np.ndarray:
+        """rows: (K, n) host frames ((n,) for K = 1) -> (n*interp,) complex64."""
+        x = _as_c(rows, C64)
+        if x.ndim == 1 and self.nch == 1:
+            x = x.reshape(1, -1)
+        if x.ndim != 2 or x.shape[0] != self.nch:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Upconverter.process: shape must be (nch, n)")
+        n_in = x.shape[1]
+        out = np.empty(max(self.output_len(n_in), 1), dtype=np.complex64)
+        got = ctypes.c_size_t()
+        check(lib().sdrgpu_upconv_process(self._h, x.ctypes.data, max(n_in, 1), n_in, out.ctypes.data,
+                                          out.size, ctypes.byref(got)), "sdrgpu_upconv_process")
+        return out[:got.value]
+
+    def process_dev(self, d_in_ptr: int, ld_in: int, n_in: int, d_out_ptr: int, cap_out: int) -> int:
+        """Enqueue on the handle's stream with device pointers; row k's frames are read from
+        d_in + k*ld_in frames.  Returns n_out."""
+        got = ctypes.c_size_t()
+        check(lib().sdrgpu_upconv_process_dev(self._h, d_in_ptr, ld_in, n_in, d_out_ptr, cap_out,
+                                              ctypes.byref(got)), "sdrgpu_upconv_process_dev")
+        return got.value
+
+    def sync(self):
+        check(lib().sdrgpu_upconv_sync(self._h), "sdrgpu_upconv_sync")
+
 
 # ---------------------------------------------------------------------- Channelizer
 class Channelizer:
