@@ -163,8 +163,8 @@ int sdrgpu_fir_process(sdrgpu_fir* h, const void* in, size_t n_in, void* out,
  * shifted): the handle then filters a device copy of the input, so the results are those of an
  * out-of-place call (the kernels store output tiles while other workgroups still read the
  * input under them).  The same holds for sdrgpu_firbank_process_dev, sdrgpu_chan_process_dev,
- * sdrgpu_synth_process_dev, sdrgpu_polyfir_process_dev, sdrgpu_tuner_process_dev, sdrgpu_fft_exec_dev,
- * sdrgpu_rfft_exec_dev and sdrgpu_stft_process_dev. */
+ * sdrgpu_synth_process_dev, sdrgpu_polyfir_process_dev, sdrgpu_tuner_process_dev,
+ * sdrgpu_demod_process_dev, sdrgpu_fft_exec_dev, sdrgpu_rfft_exec_dev and sdrgpu_stft_process_dev. */
 int sdrgpu_fir_process_dev(sdrgpu_fir* h, const void* d_in, size_t n_in, void* d_out,
                            size_t out_cap, size_t* n_out);
 /* HOST pointers, asynchronous (the Block adapter's producer/consumer split,
@@ -530,6 +530,69 @@ int sdrgpu_upconv_sync(sdrgpu_upconv* h);
 int sdrgpu_upconv_reset(sdrgpu_upconv* h);
 int sdrgpu_upconv_clone(const sdrgpu_upconv* h, sdrgpu_upconv** out);
 void sdrgpu_upconv_destroy(sdrgpu_upconv* h);
+
+/* Demodulator bank: per-sample detectors over channel rows, c64 (or u8 I/Q) in, f32 out: what
+ * turns the rows of sdrgpu_tuner / sdrgpu_chan / sdrgpu_polyfir into audio or a level without a
+ * loop-carried recurrence.  The reference has no counterpart (its only demodulator is the PLL,
+ * src/filter/pll.rs); this header is the definition.  With x = (xr, xi) the row's sample at stream
+ * index m, counted across calls, and every operation below one f32 IEEE operation rounded on its
+ * own (no FMA contraction):
+ *   SDRGPU_DEMOD_FM        re = xr*pr + xi*pi,  im = xi*pr - xr*pi,  y[m] = atan2f(im, re) * gain,
+ *                          (pr, pi) = x[m-1]: num-complex's x * prev.conj() followed by arg()
+ *                          (f32::atan2, i.e. glibc atan2f, bit for bit).  Before the first sample
+ *                          of a stream x[-1] = (1, 0), a carrier at phase 0, so y[0] is gain times
+ *                          the phase of x[0] whatever the signs of zero products.
+ *   SDRGPU_DEMOD_PHASE     y[m] = atan2f(xi, xr) * gain
+ *   SDRGPU_DEMOD_ENVELOPE  y[m] = sqrtf(xr*xr + xi*xi) * gain   (IEEE sqrtf, denormals included)
+ *   SDRGPU_DEMOD_POWER     y[m] = (xr*xr + xi*xi) * gain
+ * sdrgpu_demod_fm_gain (host only, no device): *gain = (float)(rate / (2*pi*deviation)), computed
+ * in double and rounded once; FM output is then in units of the deviation (main.rs:49's
+ * / 75000.0).  Non-finite or non-positive arguments: SDRGPU_ERR_INVALID.
+ * Layout: rows as in sdrgpu_firbank and as sdrgpu_tuner / sdrgpu_chan write them: row r starts at
+ * in + r*ld_in samples (ld_in counts samples of either kind) and at out + r*ld_out floats; n
+ * outputs per row; the gaps between rows are neither read nor written (except by the device copy
+ * of an overlapped call, below, which reads the input span).
+ * Kinds: samples SDRGPU_C64, or SDRGPU_CU8 with (v-128)/128 fused into the load.
+ * State, on the device: the last sample of each row (c64, after the u8 conversion).  Every mode
+ * carries it, only FM reads it.  reset returns it to (1, 0); a clone keeps mode, gain and state
+ * and gets its own stream.  sdrgpu_demod_set_gain takes effect at the next process call and is
+ * ordered after the calls enqueued before it (the gain travels with each call).
+ * Partitions: any partition of a stream into calls, n = 0 and 1-sample calls included, is
+ * bit-identical.  Rows: row r of an nch-row handle is bit-identical to an nch = 1 handle fed row r.
+ * Non-finite samples: in FM a non-finite x[q] makes exactly y[q] and y[q+1] depend on it, in the
+ * other modes exactly y[q]; every other output is bit-identical to a clean run, and the affected
+ * outputs hold what the formulas above give for those operands.
+ * d_out may overlap d_in (see sdrgpu_fir_process_dev).
+ * Limits, checked before the device is looked at: a null pointer, nch == 0, or a kind or mode
+ * outside its enum: SDRGPU_ERR_INVALID; SDRGPU_F32 samples or nch > 65536: SDRGPU_ERR_UNSUPPORTED.
+ * ld_in < n or ld_out < n: SDRGPU_ERR_INVALID with no state touched.  n = 0 is OK and does
+ * nothing. */
+typedef struct sdrgpu_demod sdrgpu_demod;
+
+enum sdrgpu_demod_mode {
+    SDRGPU_DEMOD_FM = 0,
+    SDRGPU_DEMOD_PHASE = 1,
+    SDRGPU_DEMOD_ENVELOPE = 2,
+    SDRGPU_DEMOD_POWER = 3,
+};
+
+int sdrgpu_demod_fm_gain(double rate, double deviation, float* gain);
+int sdrgpu_demod_create(int device, int sample_kind, int mode, float gain, size_t nch,
+                        sdrgpu_demod** out);
+int sdrgpu_demod_set_gain(sdrgpu_demod* h, float gain);
+int sdrgpu_demod_get_gain(const sdrgpu_demod* h, float* gain);
+int sdrgpu_demod_get_mode(const sdrgpu_demod* h, int* mode);
+int sdrgpu_demod_set_stream(sdrgpu_demod* h, void* hip_stream);
+int sdrgpu_demod_get_stream(const sdrgpu_demod* h, void** hip_stream);
+int sdrgpu_demod_output_len(const sdrgpu_demod* h, size_t n_in, size_t* n_out);  /* n_in */
+int sdrgpu_demod_process(sdrgpu_demod* h, const void* in, size_t ld_in, size_t n, float* out,
+                         size_t ld_out);
+int sdrgpu_demod_process_dev(sdrgpu_demod* h, const void* d_in, size_t ld_in, size_t n, float* d_out,
+                             size_t ld_out);
+int sdrgpu_demod_sync(sdrgpu_demod* h);
+int sdrgpu_demod_reset(sdrgpu_demod* h);
+int sdrgpu_demod_clone(const sdrgpu_demod* h, sdrgpu_demod** out);
+void sdrgpu_demod_destroy(sdrgpu_demod* h);
 
 /* =====================================================================================
  * FFT.

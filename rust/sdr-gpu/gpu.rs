@@ -615,6 +615,110 @@ impl Drop for GpuTuner {
     }
 }
 
+// ---------------------------------------------------------------- demodulator bank
+
+/// What a `GpuDemod` computes per sample (include/sdrgpu.h `sdrgpu_demod_mode`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum DemodMode {
+    /// `(x * prev.conj()).arg() * gain`, `prev` starting at `(1, 0)`
+    Fm,
+    /// `x.arg() * gain`
+    Phase,
+    /// `(re*re + im*im).sqrt() * gain`
+    Envelope,
+    /// `(re*re + im*im) * gain`
+    Power,
+}
+
+impl DemodMode {
+    fn code(self) -> i32 {
+        match self {
+            DemodMode::Fm => sys::SDRGPU_DEMOD_FM,
+            DemodMode::Phase => sys::SDRGPU_DEMOD_PHASE,
+            DemodMode::Envelope => sys::SDRGPU_DEMOD_ENVELOPE,
+            DemodMode::Power => sys::SDRGPU_DEMOD_POWER,
+        }
+    }
+}
+
+/// A per-sample detector over `nch` rows of `Complex<f32>` samples, f32 out (include/sdrgpu.h
+/// `sdrgpu_demod`): what turns the rows of `GpuTuner`, `Channelizer` or `PolyFir` into audio or
+/// a level.  Every operation is one f32 operation and `arg()` is `f32::atan2` bit for bit, so
+/// `DemodMode::Fm` equals `.map(|x| (x * prev.conj()).arg() * gain)` sample for sample.  State
+/// is the last sample of each row; any partition into blocks gives the same bits.
+pub struct GpuDemod {
+    h: *mut sys::sdrgpu_demod,
+    nch: usize,
+}
+
+unsafe impl Send for GpuDemod {}
+
+impl GpuDemod {
+    /// `rate / (2 pi deviation)` rounded once to f32 (`sdrgpu_demod_fm_gain`): FM output in
+    /// units of the deviation, the job of main.rs:49's `/ 75000.0`.
+    pub fn fm_gain(rate: f64, deviation: f64) -> Result<f32> {
+        let mut g = 0.0;
+        check(unsafe { sys::sdrgpu_demod_fm_gain(rate, deviation, &mut g) })?;
+        Ok(g)
+    }
+
+    /// `nch`: 1..=65536 rows.
+    pub fn new(mode: DemodMode, gain: f32, nch: usize) -> Result<Self> {
+        let mut h = ptr::null_mut();
+        check(unsafe { sys::sdrgpu_demod_create(DEVICE, sys::SDRGPU_C64, mode.code(), gain, nch, &mut h) })?;
+        Ok(GpuDemod { h, nch })
+    }
+
+    /// The quadrature FM discriminator for rows at `rate` samples per second.
+    pub fn fm(rate: f64, deviation: f64, nch: usize) -> Result<Self> {
+        Self::new(DemodMode::Fm, Self::fm_gain(rate, deviation)?, nch)
+    }
+
+    /// From the next `process` call on.
+    pub fn set_gain(&mut self, gain: f32) -> Result<()> {
+        check(unsafe { sys::sdrgpu_demod_set_gain(self.h, gain) })
+    }
+
+    pub fn gain(&self) -> f32 {
+        let mut g = 0.0;
+        check(unsafe { sys::sdrgpu_demod_get_gain(self.h, &mut g) }).expect("sdrgpu_demod_get_gain");
+        g
+    }
+
+    /// One block: `input` holds `nch` rows of `n` samples back to back (the layout `GpuTuner`
+    /// writes); `output` gets `nch` rows of `n` f32.
+    pub fn process(&mut self, input: &[Complex<f32>], output: &mut Vec<f32>) -> Result<usize> {
+        let n = input.len() / self.nch;
+        if n * self.nch != input.len() {
+            return Err(Error(sys::SDRGPU_ERR_INVALID));
+        }
+        output.resize(self.nch * n, 0.0);
+        check(unsafe {
+            sys::sdrgpu_demod_process(self.h, input.as_ptr() as *const _, n, n, output.as_mut_ptr(), n)
+        })?;
+        Ok(n)
+    }
+
+    pub fn reset(&mut self) -> Result<()> {
+        check(unsafe { sys::sdrgpu_demod_reset(self.h) })
+    }
+}
+
+impl Clone for GpuDemod {
+    // the copy carries the mode, the gain and the last sample of each row
+    fn clone(&self) -> Self {
+        let mut h = ptr::null_mut();
+        check(unsafe { sys::sdrgpu_demod_clone(self.h, &mut h) }).expect("sdrgpu_demod_clone");
+        GpuDemod { h, nch: self.nch }
+    }
+}
+
+impl Drop for GpuDemod {
+    fn drop(&mut self) {
+        unsafe { sys::sdrgpu_demod_destroy(self.h) }
+    }
+}
+
 // -------------------------------------------------------------- up-converter bank
 
 /// One row of `Complex<f32>` frames per tuning word onto one wideband stream (include/sdrgpu.h

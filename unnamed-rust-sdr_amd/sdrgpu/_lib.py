@@ -45,6 +45,11 @@ FFT_OUT_DB = 1
 PLL_OUT_FILTER = 0
 PLL_OUT_STEREO_DIFF = 1
 
+DEMOD_FM = 0
+DEMOD_PHASE = 1
+DEMOD_ENVELOPE = 2
+DEMOD_POWER = 3
+
 DEBUG_ATAN2F = 0
 DEBUG_SINCOSF = 1
 
@@ -213,6 +218,21 @@ SIGNATURES = [
     ("sdrgpu_upconv_reset", c_int, [_H]),
     ("sdrgpu_upconv_clone", c_int, [_H, _PH]),
     ("sdrgpu_upconv_destroy", None, [_H]),
+    # demodulator bank
+    ("sdrgpu_demod_fm_gain", c_int, [ctypes.c_double, ctypes.c_double, POINTER(c_float)]),
+    ("sdrgpu_demod_create", c_int, [c_int, c_int, c_int, c_float, c_size_t, _PH]),
+    ("sdrgpu_demod_set_gain", c_int, [_H, c_float]),
+    ("sdrgpu_demod_get_gain", c_int, [_H, POINTER(c_float)]),
+    ("sdrgpu_demod_get_mode", c_int, [_H, POINTER(c_int)]),
+    ("sdrgpu_demod_set_stream", c_int, [_H, c_void_p]),
+    ("sdrgpu_demod_get_stream", c_int, [_H, _PH]),
+    ("sdrgpu_demod_output_len", c_int, [_H, c_size_t, _PS]),
+    ("sdrgpu_demod_process", c_int, [_H, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t]),
+    ("sdrgpu_demod_process_dev", c_int, [_H, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t]),
+    ("sdrgpu_demod_sync", c_int, [_H]),
+    ("sdrgpu_demod_reset", c_int, [_H]),
+    ("sdrgpu_demod_clone", c_int, [_H, _PH]),
+    ("sdrgpu_demod_destroy", None, [_H]),
     # FFT
     ("sdrgpu_fft_plan", c_int, [c_int, c_size_t, _PH]),
     ("sdrgpu_fft_set_stream", c_int, [_H, c_void_p]),

@@ -536,6 +536,122 @@ class Tuner:
         return Upconverter(taps, self.decim, rate=self.rate, words=self.words, device=self.device)
 
 
+# ---------------------------------------------------------------------------- Demod
+def demod_fm_gain(rate: float, deviation: float) -> float:
+    """(float)(rate / (2 pi deviation)), rounded once (sdrgpu_demod_fm_gain; no device): the gain
+    that puts an FM discriminator's output in units of the deviation."""
+    g = ctypes.c_float()
+    check(lib().sdrgpu_demod_fm_gain(float(rate), float(deviation), ctypes.byref(g)),
+          "sdrgpu_demod_fm_gain")
+    return g.value
+
+
+class Demod:
+    """Demodulator bank (sdrgpu_demod): a per-sample detector over `nch` channel rows, c64 or
+    rtl_tcp CU8 in, f32 out, each operation one f32 IEEE operation:
+
+      DEMOD_FM        atan2f(im, re) * gain of x[m] * conj(x[m-1]); x[-1] = (1, 0)
+      DEMOD_PHASE     atan2f(xi, xr) * gain
+      DEMOD_ENVELOPE  sqrtf(xr*xr + xi*xi) * gain
+      DEMOD_POWER     (xr*xr + xi*xi) * gain
+
+    atan2f is glibc's bit for bit (what num-complex's arg() calls).  The reference has no such
+    stage (its only demodulator is the PLL, pll.rs).  State is the last sample per row and carries
+    across blocks, so any partition into blocks gives the same bits; rows are independent."""
+
+    def __init__(self, mode: int, gain: float = 1.0, nch: int = 1, sample_kind: int = C64,
+                 device: int = 0, _handle=None):
+        self.mode = int(mode)
+        self.nch = int(nch)
+        self.sample_kind = sample_kind
+        self.device = device
+        self._h = ctypes.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            check(lib().sdrgpu_demod_create(device, sample_kind, self.mode, float(gain), self.nch,
+                                            ctypes.byref(self._h)), "sdrgpu_demod_create")
+
+    @classmethod
+    def fm(cls, rate: float, deviation: float, nch: int = 1, sample_kind: int = C64,
+           device: int = 0) -> "Demod":
+        """The quadrature FM discriminator at sample rate `rate`, output in units of `deviation`."""
+        return cls(_lib.DEMOD_FM, demod_fm_gain(rate, deviation), nch, sample_kind, device)
+
+    def close(self):
+        if self._h:
+            lib().sdrgpu_demod_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def gain(self) -> float:
+        g = ctypes.c_float()
+        check(lib().sdrgpu_demod_get_gain(self._h, ctypes.byref(g)), "sdrgpu_demod_get_gain")
+        return g.value
+
+    def set_gain(self, gain: float):
+        """From the next process call on; ordered after the calls enqueued before it."""
+        check(lib().sdrgpu_demod_set_gain(self._h, float(gain)), "sdrgpu_demod_set_gain")
+
+    def clone(self) -> "Demod":
+        h = ctypes.c_void_p()
+        check(lib().sdrgpu_demod_clone(self._h, ctypes.byref(h)), "sdrgpu_demod_clone")
+        return Demod(self.mode, nch=self.nch, sample_kind=self.sample_kind, device=self.device,
+                     _handle=h)
+
+    def reset(self):
+        check(lib().sdrgpu_demod_reset(self._h), "sdrgpu_demod_reset")
+
+    def set_stream(self, stream_ptr: Optional[int]):
+        check(lib().sdrgpu_demod_set_stream(self._h, stream_ptr), "sdrgpu_demod_set_stream")
+
+    def stream(self) -> int:
+        s = ctypes.c_void_p()
+        check(lib().sdrgpu_demod_get_stream(self._h, ctypes.byref(s)), "sdrgpu_demod_get_stream")
+        return s.value or 0
+
+    def output_len(self, n_in: int) -> int:
+        n = ctypes.c_size_t()
+        check(lib().sdrgpu_demod_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
+        return n.value
+
+    def process(self, x) -> np.ndarray:
+        """x: (n,) for nch = 1, else (nch, n) host samples (CU8: 2n bytes per row, or (.., n, 2))
+        -> (n,) or (nch, n) float32."""
+        x = _as_c(x, self.sample_kind)
+        u8 = self.sample_kind == CU8
+        # one row as (n, 2) byte pairs; a (1, 2) array is one row of one sample
+        flat = self.nch == 1 and (x.ndim == 1 or u8 and x.ndim == 2 and x.shape[1] == 2 and x.shape[0] != 1)
+        if flat:
+            x = x.reshape(1, -1)
+        elif u8 and x.ndim == 3:
+            x = x.reshape(x.shape[0], -1)
+        if x.ndim != 2 or x.shape[0] != self.nch or u8 and x.shape[1] % 2:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Demod.process: shape must be (nch, n)")
+        n = x.shape[1] // 2 if self.sample_kind == CU8 else x.shape[1]
+        out = np.empty((self.nch, max(n, 1)), dtype=np.float32)
+        check(lib().sdrgpu_demod_process(self._h, x.ctypes.data, n, n,
+                                         out.ctypes.data, out.shape[1]), "sdrgpu_demod_process")
+        y = out[:, :n]
+        return y[0] if flat else y
+
+    def process_dev(self, d_in_ptr: int, ld_in: int, n: int, d_out_ptr: int, ld_out: int) -> int:
+        """Enqueue on the handle's stream with device pointers; row r is read at d_in + r*ld_in
+        samples and written at d_out + r*ld_out floats.  Returns n."""
+        check(lib().sdrgpu_demod_process_dev(self._h, d_in_ptr, ld_in, n, d_out_ptr, ld_out),
+              "sdrgpu_demod_process_dev")
+        return n
+
+    def sync(self):
+        check(lib().sdrgpu_demod_sync(self._h), "sdrgpu_demod_sync")
+
+
 # ---------------------------------------------------------------------------- Upconverter
 class Upconverter:
     """Up-converter bank (digital up-converter, sdrgpu_upconv): K rows of c64 frames onto any

@@ -12,6 +12,11 @@ file or the audio card, stage for stage:
   main.rs:52,73-81 de-emphasis Lr on mono and diff       -> one 2-channel Biquad bank
                    -> (mono + diff, mono - diff)
 
+`demod="quadrature"` (receiver, and `stations` for channel rows) puts the quadrature discriminator
+`filter.Demod.fm(rate, 75000)` -- arg(x[m] * conj(x[m-1])) * rate / (2 pi 75000), stateless apart
+from one sample per row -- in the discriminator PLL's place; every later stage, the pilot PLL
+included, is unchanged.  The default `demod="pll"` is the reference's chain.
+
 The `block(0.1)` stages are the reference's threading (src/signal/adapters/block.rs) and
 `monitor` prints; neither changes a sample, so they are not stages here.  Every GPU stage is
 bit-exact to its oracle restatement (tests/test_fm_chain_gpu.py checks the whole chain); the
@@ -46,17 +51,29 @@ def deemphasis() -> "_filter.BiquadD":
     return _filter.BiquadD.Lr(float(np.float32(1.0) / (np.float32(75.0) * np.float32(0.001) * np.float32(0.001))))
 
 
-def receiver(rtl):
+def _check_demod(demod: str, where: str) -> bool:
+    """True for the quadrature discriminator, False for the reference's PLL."""
+    if demod not in ("pll", "quadrature"):
+        raise _lib.SdrGpuError(_lib.ERR_INVALID, f'{where}: demod must be "pll" or "quadrature"')
+    return demod == "quadrature"
+
+
+def receiver(rtl, demod: str = "pll"):
     """src/main.rs:48-81 over `rtl` (rtl_tcp bytes at 1.8 Msps): Signal of (n, 2) f32 frames
     (left, right) at 48 kHz.  Like every other stage, the pilot PLL and the de-emphasis bank
     are built inside the generators, so each iteration of the returned Signal starts from
-    fresh filter state (the reference builds its chain once per run, main.rs:33-81)."""
+    fresh filter state (the reference builds its chain once per run, main.rs:33-81).
+    demod="quadrature" replaces main.rs:41-47 with Demod.fm(rate, 75000) on the raw bytes."""
     from .signal import Signal
+    quad = _check_demod(demod, "fm.receiver")
     if rtl.sample_kind != _lib.CU8:
         raise _lib.SdrGpuError(_lib.ERR_INVALID, "fm.receiver: expects rtl_tcp u8 I/Q (CU8)")
     dev = np.float32(DEVIATION)
-    fm = rtl.filter(discriminator_design()).map(
-        lambda r: np.where(r["locked"], r["value"], np.float32(0.0)).astype(np.float32) / dev)
+    if quad:
+        fm = rtl.demod_fm(DEVIATION)
+    else:
+        fm = rtl.filter(discriminator_design()).map(
+            lambda r: np.where(r["locked"], r["value"], np.float32(0.0)).astype(np.float32) / dev)
     audio = fm.resample_with(_resample.ConverterType.SincFastest, 48000.0 * 3.0)
 
     def stereo():  # main.rs:54-69 with the pilot PLL on the GPU (state carried per block)
@@ -134,7 +151,10 @@ def receivers(wideband, nch: int, taps, oversample: int = 2, rate_taps=None):
     rate_taps = (h1, h2) replaces the two sinc converters with rational-rate polyphase FIRs on the
     caller's taps: PolyFir(h1, up1, down1, nch) with up1/down1 the exact fraction
     144000 / row rate (ERR_UNSUPPORTED where there is none within the PolyFir's limits), and
-    PolyFir(h2, 1, 3, 2 nch).  The default None leaves the chain above as it is."""
+    PolyFir(h2, 1, 3, 2 nch).  The default None leaves the chain above as it is.
+
+    Everything after the Channelizer is `stations`, which also offers the quadrature
+    discriminator."""
     if wideband.sample_kind not in (_lib.C64, _lib.CU8):
         raise _lib.SdrGpuError(_lib.ERR_INVALID, "fm.receivers: expects a c64 or CU8 Signal")
     kind = wideband.sample_kind
@@ -148,7 +168,7 @@ def receivers(wideband, nch: int, taps, oversample: int = 2, rate_taps=None):
         for b in wideband.blocks():
             yield chan.process(b)
 
-    return _stations(rows, nch, row_rate, rate_taps)
+    return stations(rows, nch, row_rate, rate_taps)
 
 
 def tuned_receivers(wideband, freqs, decim: int, taps, rate_taps=None):
@@ -158,7 +178,7 @@ def tuned_receivers(wideband, freqs, decim: int, taps, rate_taps=None):
 
       Tuner(taps, decim, freqs, rate)                 -> (K, n) c64 at rate / decim
 
-    and then every stage of `receivers` on the rows; rate_taps as there."""
+    and then every stage of `receivers` on the rows (`stations`); rate_taps as there."""
     if wideband.sample_kind not in (_lib.C64, _lib.CU8):
         raise _lib.SdrGpuError(_lib.ERR_INVALID, "fm.tuned_receivers: expects a c64 or CU8 Signal")
     kind = wideband.sample_kind
@@ -173,13 +193,18 @@ def tuned_receivers(wideband, freqs, decim: int, taps, rate_taps=None):
         for b in wideband.blocks():
             yield tuner.process(b)
 
-    return _stations(rows, len(freqs), rate / int(decim), rate_taps)
+    return stations(rows, len(freqs), rate / int(decim), rate_taps)
 
 
-def _stations(front, nch: int, row_rate: float, rate_taps):
-    """What follows the front end in `receivers` and `tuned_receivers`: `front()` yields
-    (nch, n) c64 blocks of station rows at row_rate."""
+def stations(front, nch: int, row_rate: float, rate_taps=None, demod: str = "pll"):
+    """What follows the front end in `receivers` and `tuned_receivers`, for any front end:
+    `front()` yields (nch, n) c64 blocks of station rows at row_rate (a Tuner's, a Channelizer's,
+    a PolyFir's) -> Signal of (nch, n, 2) f32 blocks, (left, right) at 48 kHz; rate_taps as in
+    `receivers`.  demod="quadrature" puts a Demod.fm(row_rate, 75000) bank of nch rows in the
+    discriminator Pll bank's place (its output is already in units of the deviation); every later
+    stage is unchanged.  The default "pll" is the chain `receivers` and `tuned_receivers` run."""
     from .signal import Signal
+    quad = _check_demod(demod, "fm.stations")
     dev = np.float32(DEVIATION)
     r1 = float(np.float32(48000.0 * 3.0)) / float(np.float32(row_rate))
     r2 = float(np.float32(48000.0)) / float(np.float32(48000.0 * 3.0))
@@ -200,6 +225,12 @@ def _stations(front, nch: int, row_rate: float, rate_taps):
     def fm():
         disc = None
         for rows in front():
+            if quad:
+                if disc is None:
+                    disc = _filter.Demod.fm(row_rate, DEVIATION, nch=nch)
+                if rows.shape[1]:
+                    yield disc.process(rows)
+                continue
             if disc is None:
                 disc = discriminator_design().design(row_rate, nch=nch)
             if rows.shape[1]:

@@ -182,6 +182,28 @@ class Signal:
                     yield y
         return Signal(self._rate / decim, gen, _lib.C64)
 
+    def demod(self, mode: int, gain: float = 1.0) -> "Signal":
+        """A per-sample detector on a c64 or CU8 Signal (filter.Demod with one row): mode one of
+        _lib.DEMOD_FM / DEMOD_PHASE / DEMOD_ENVELOPE / DEMOD_POWER, output f32 at the same rate.
+        DEMOD_FM is .map(|x| (x * prev.conj()).arg() * gain) with prev starting at (1, 0)."""
+        sk = self.sample_kind
+        if sk == _lib.F32:
+            raise _lib.SdrGpuError(_lib.ERR_UNSUPPORTED, "demod: F32 samples")
+        src = self
+
+        def gen():
+            d = _filter.Demod(mode, gain, 1, sample_kind=_lib.CU8 if sk == _lib.CU8 else _lib.C64)
+            for b in src.blocks():
+                y = d.process(np.asarray(b).reshape(-1))
+                if y.size:
+                    yield y
+        return Signal(self._rate, gen, _lib.F32)
+
+    def demod_fm(self, deviation: float) -> "Signal":
+        """The quadrature FM discriminator, output in units of `deviation` Hz at this Signal's
+        rate (gain = rate / (2 pi deviation), sdrgpu_demod_fm_gain)."""
+        return self.demod(_lib.DEMOD_FM, _filter.demod_fm_gain(self._rate, deviation))
+
     def resample(self, rate: float) -> "Signal":
         """Signal::resample (src/signal/mod.rs:78-84): SincBestQuality (this library's own
         sinc table)."""
