@@ -594,6 +594,96 @@ int sdrgpu_demod_reset(sdrgpu_demod* h);
 int sdrgpu_demod_clone(const sdrgpu_demod* h, sdrgpu_demod** out);
 void sdrgpu_demod_destroy(sdrgpu_demod* h);
 
+/* AGC bank: a gain loop over channel rows, c64 or f32 in, the same kind out: what levels the rows
+ * of sdrgpu_tuner / sdrgpu_chan before sdrgpu_demod's envelope detector, or rows on their way into
+ * sdrgpu_upconv.  The reference has no counterpart; this header is the definition.  The gain moves
+ * once per frame of `frame` samples, from that frame's mean magnitude, so that everything per
+ * sample is parallel and the only serial work is n / frame short steps per row; frame = 1 is the
+ * classic per-sample loop g += rate * (reference - |x*g|), correct but serial.
+ * Per-row state is (g, s, c): the gain, the open frame's partial sum and the samples counted in
+ * it.  After create or reset g = clamp(initial_gain) (the clamp below), s = 0, c = 0.  Frames are
+ * aligned to the absolute stream index, counted across calls.  With x = (xr, xi) the row's sample
+ * at stream index m and every line below one f32 IEEE operation rounded on its own (no FMA
+ * contraction):
+ *   a       = sqrtf(xr*xr + xi*xi)        SDRGPU_C64 (IEEE sqrtf, as SDRGPU_DEMOD_ENVELOPE)
+ *   a       = fabsf(x)                    SDRGPU_F32
+ *   y[m]    = (xr*g, xi*g)                SDRGPU_F32: x*g
+ *   gain[m] = g                           the optional second output row, f32
+ *   s = s + a;  c = c + 1
+ *   if c == frame:
+ *       lvl = (s / (float)frame) * g      one IEEE division, one product
+ *       d   = reference - lvl
+ *       r   = d < 0 ? attack : decay
+ *       g1  = g + r*d                     product, then sum
+ *       g   = !(g1 >= min_gain) ? min_gain : (g1 > max_gain ? max_gain : g1)
+ *       s = 0;  c = 0
+ * so a sample is scaled with the gain its frame started with, and a frame's magnitudes are added in
+ * stream order.  attack is the rate at which the gain falls (the level is above the reference),
+ * decay the rate at which it rises.
+ * Layout: rows as in sdrgpu_demod: row r starts at in + r*ld_in samples, at out + r*ld_out samples
+ * (both of the handle's kind) and at gain + r*ld_gain floats; n outputs per row; the gaps between
+ * rows are neither read nor written (except by the device copy of an overlapped call, below).
+ * gain may be NULL; ld_gain is then ignored.  out and gain must not overlap each other.
+ * sdrgpu_agc_set_design replaces every field but frame (its frame field is ignored), keeps the
+ * state, takes effect at the next process call and is ordered after the calls enqueued before it
+ * (the design travels with each call).  sdrgpu_agc_get_gains waits for the handle's stream and
+ * writes the nch current gains: reference / gains[r] is row r's level, its RSSI.  reset returns
+ * the state to (clamp(initial_gain), 0, 0); a clone keeps design and state, mid-frame included,
+ * and gets its own stream.
+ * Partitions: any partition of a stream into calls, n = 0, 1-sample calls and calls that end
+ * mid-frame included, is bit-identical.  Rows: row r of an nch-row handle is bit-identical to an
+ * nch = 1 handle fed row r.  Output length is n.
+ * Non-finite samples: the clamp is written with comparisons, so a NaN g1 becomes min_gain.  A
+ * non-finite x[q] makes y[q] non-finite and drops the gain to min_gain at the end of q's frame;
+ * every other output is finite and equals what the formulas above give.  The reach of one bad
+ * sample is therefore one frame at min_gain followed by the loop's recovery at the decay rate, not
+ * a bounded window.
+ * In place: d_out == d_in with ld_out == ld_in runs with no copy (and, for SDRGPU_F32, so does
+ * d_gain == d_in with ld_gain == ld_in).  Every other overlap of an output with the input runs on
+ * a device copy of the input span, as in sdrgpu_fir_process_dev.  sdrgpu_agc_last_plan reports the
+ * most recent non-empty call: *form 0 (the call stayed inside the open frame: no level pass), 1
+ * (frame sums from LDS tiles) or 2 (frame sums streamed from memory), -1 before the first call;
+ * *copied 1 if the input was copied.  Introspection for tests and benches.
+ * Cost: everything per sample is parallel and streams at about the rate of sdrgpu_demod's
+ * envelope; the serial part is one lane per row taking n / frame dependent steps of about 50 ns
+ * each on an MI355X, whatever the number of rows up to a few thousand.  So prefer
+ * a frame for which n / frame stays in the thousands per call: 2^26 samples of one row take 1.4 ms
+ * with frame = 4096 and 54 ms with frame = 64; frame = 1 costs 51 ns per sample.
+ * Limits, checked before the device is looked at: a null pointer, nch == 0, frame == 0, a kind
+ * outside its enum, a non-finite or non-positive reference, min_gain or max_gain, min_gain >
+ * max_gain, attack or decay outside (0, 1]: SDRGPU_ERR_INVALID; SDRGPU_CU8, frame > 4096 or
+ * nch > 65536: SDRGPU_ERR_UNSUPPORTED.  ld_in < n, ld_out < n or (with gain) ld_gain < n:
+ * SDRGPU_ERR_INVALID with no state touched.  n = 0 is OK and does nothing. */
+typedef struct sdrgpu_agc sdrgpu_agc;
+
+typedef struct {
+    float reference;      /* the level the loop steers |y| to */
+    float attack;         /* rate while the level is above the reference, (0, 1] */
+    float decay;          /* rate while it is below, (0, 1] */
+    float min_gain;
+    float max_gain;
+    float initial_gain;
+    uint32_t frame;       /* samples per gain step, 1 .. 4096 */
+} sdrgpu_agc_design;
+
+int sdrgpu_agc_create(int device, int sample_kind, const sdrgpu_agc_design* design, size_t nch,
+                      sdrgpu_agc** out);
+int sdrgpu_agc_set_design(sdrgpu_agc* h, const sdrgpu_agc_design* design);
+int sdrgpu_agc_get_design(const sdrgpu_agc* h, sdrgpu_agc_design* design);
+int sdrgpu_agc_get_gains(const sdrgpu_agc* h, float* nch_gains);
+int sdrgpu_agc_last_plan(const sdrgpu_agc* h, int* form, int* copied);
+int sdrgpu_agc_set_stream(sdrgpu_agc* h, void* hip_stream);
+int sdrgpu_agc_get_stream(const sdrgpu_agc* h, void** hip_stream);
+int sdrgpu_agc_output_len(const sdrgpu_agc* h, size_t n_in, size_t* n_out);  /* n_in */
+int sdrgpu_agc_process(sdrgpu_agc* h, const void* in, size_t ld_in, size_t n, void* out,
+                       size_t ld_out, float* gain, size_t ld_gain);
+int sdrgpu_agc_process_dev(sdrgpu_agc* h, const void* d_in, size_t ld_in, size_t n, void* d_out,
+                           size_t ld_out, float* d_gain, size_t ld_gain);
+int sdrgpu_agc_sync(sdrgpu_agc* h);
+int sdrgpu_agc_reset(sdrgpu_agc* h);
+int sdrgpu_agc_clone(const sdrgpu_agc* h, sdrgpu_agc** out);
+void sdrgpu_agc_destroy(sdrgpu_agc* h);
+
 /* =====================================================================================
  * FFT.
  * Replaces: fft::fft  (src/fft.rs:3-28)  -- forward DFT, fftshift collate, x 1/sqrt(N)

@@ -719,6 +719,107 @@ impl Drop for GpuDemod {
     }
 }
 
+// ------------------------------------------------------------------------ AGC bank
+
+/// The loop of a `GpuAgc` (include/sdrgpu.h `sdrgpu_agc_design`): the gain moves once per `frame`
+/// samples, `g += (d < 0 ? attack : decay) * d` with `d = reference - mean|x| * g`, clamped to
+/// `[min_gain, max_gain]`.
+pub type AgcDesign = sys::sdrgpu_agc_design;
+
+/// A frame-rate gain loop over `nch` rows of `Complex<f32>` samples, the same kind out
+/// (include/sdrgpu.h `sdrgpu_agc`): what levels the rows of `GpuTuner` or `Channelizer` before
+/// `GpuDemod`'s envelope detector.  Every operation is one f32 operation; state is the gain, the
+/// open frame's partial sum and its sample count per row, so any partition into blocks gives the
+/// same bits.
+pub struct GpuAgc {
+    h: *mut sys::sdrgpu_agc,
+    nch: usize,
+}
+
+unsafe impl Send for GpuAgc {}
+
+impl GpuAgc {
+    /// `nch`: 1..=65536 rows; `design.frame`: 1..=4096.
+    pub fn new(design: &AgcDesign, nch: usize) -> Result<Self> {
+        let mut h = ptr::null_mut();
+        check(unsafe { sys::sdrgpu_agc_create(DEVICE, sys::SDRGPU_C64, design, nch, &mut h) })?;
+        Ok(GpuAgc { h, nch })
+    }
+
+    /// Every field but `frame`, from the next `process` call on; the state is kept.
+    pub fn set_design(&mut self, design: &AgcDesign) -> Result<()> {
+        check(unsafe { sys::sdrgpu_agc_set_design(self.h, design) })
+    }
+
+    pub fn design(&self) -> AgcDesign {
+        let mut d = AgcDesign {
+            reference: 0.0,
+            attack: 0.0,
+            decay: 0.0,
+            min_gain: 0.0,
+            max_gain: 0.0,
+            initial_gain: 0.0,
+            frame: 0,
+        };
+        check(unsafe { sys::sdrgpu_agc_get_design(self.h, &mut d) }).expect("sdrgpu_agc_get_design");
+        d
+    }
+
+    /// The current gain of every row, after the blocks processed so far: `reference / gains()[r]`
+    /// is row r's level.
+    pub fn gains(&self) -> Result<Vec<f32>> {
+        let mut g = vec![0.0f32; self.nch];
+        check(unsafe { sys::sdrgpu_agc_get_gains(self.h, g.as_mut_ptr()) })?;
+        Ok(g)
+    }
+
+    /// One block: `input` holds `nch` rows of `n` samples back to back (the layout `GpuTuner`
+    /// writes); `output` gets the levelled rows in the same layout and, if given, `gain` the gain
+    /// each sample was scaled with.
+    pub fn process(
+        &mut self,
+        input: &[Complex<f32>],
+        output: &mut Vec<Complex<f32>>,
+        gain: Option<&mut Vec<f32>>,
+    ) -> Result<usize> {
+        let n = input.len() / self.nch;
+        if n * self.nch != input.len() {
+            return Err(Error(sys::SDRGPU_ERR_INVALID));
+        }
+        output.resize(self.nch * n, Complex::new(0.0, 0.0));
+        let gp = match gain {
+            Some(g) => {
+                g.resize(self.nch * n, 0.0);
+                g.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        check(unsafe {
+            sys::sdrgpu_agc_process(self.h, input.as_ptr() as *const _, n, n, output.as_mut_ptr() as *mut _, n, gp, n)
+        })?;
+        Ok(n)
+    }
+
+    pub fn reset(&mut self) -> Result<()> {
+        check(unsafe { sys::sdrgpu_agc_reset(self.h) })
+    }
+}
+
+impl Clone for GpuAgc {
+    // the copy carries the design and every row's gain, partial frame sum and count
+    fn clone(&self) -> Self {
+        let mut h = ptr::null_mut();
+        check(unsafe { sys::sdrgpu_agc_clone(self.h, &mut h) }).expect("sdrgpu_agc_clone");
+        GpuAgc { h, nch: self.nch }
+    }
+}
+
+impl Drop for GpuAgc {
+    fn drop(&mut self) {
+        unsafe { sys::sdrgpu_agc_destroy(self.h) }
+    }
+}
+
 // -------------------------------------------------------------- up-converter bank
 
 /// One row of `Complex<f32>` frames per tuning word onto one wideband stream (include/sdrgpu.h

@@ -8,8 +8,8 @@ without the built library raises ImportError.
 from . import _lib
 from ._lib import C64, CU8, F32, SdrGpuError, device_count, lib
 from . import device, fft, filter, resample, rtltcp, shard, signal  # noqa: F401
-from .filter import Channelizer, Demod, PolyFir, Synthesizer, Tuner, Upconverter
+from .filter import Agc, Channelizer, Demod, PolyFir, Synthesizer, Tuner, Upconverter
 
 lib()  # fail loudly at import if the HIP library is missing
 
-__all__ = ["device", "fft", "filter", "resample", "rtltcp", "shard", "signal", "C64", "CU8", "F32", "SdrGpuError", "device_count", "lib", "Channelizer", "Demod", "PolyFir", "Synthesizer", "Tuner", "Upconverter"]
+__all__ = ["device", "fft", "filter", "resample", "rtltcp", "shard", "signal", "C64", "CU8", "F32", "SdrGpuError", "device_count", "lib", "Agc", "Channelizer", "Demod", "PolyFir", "Synthesizer", "Tuner", "Upconverter"]

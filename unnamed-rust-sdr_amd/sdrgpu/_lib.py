@@ -50,6 +50,10 @@ DEMOD_PHASE = 1
 DEMOD_ENVELOPE = 2
 DEMOD_POWER = 3
 
+AGC_SHORT = 0
+AGC_LDS = 1
+AGC_STREAM = 2
+
 DEBUG_ATAN2F = 0
 DEBUG_SINCOSF = 1
 
@@ -74,6 +78,11 @@ class PllParamsC(ctypes.Structure):
         ("outputf", BiquadDesignC),
         ("lockf", BiquadDesignC),
     ]
+
+
+class AgcDesignC(ctypes.Structure):
+    _fields_ = [("reference", c_float), ("attack", c_float), ("decay", c_float), ("min_gain", c_float),
+                ("max_gain", c_float), ("initial_gain", c_float), ("frame", ctypes.c_uint32)]
 
 
 class SdrGpuError(RuntimeError):
@@ -233,6 +242,21 @@ SIGNATURES = [
     ("sdrgpu_demod_reset", c_int, [_H]),
     ("sdrgpu_demod_clone", c_int, [_H, _PH]),
     ("sdrgpu_demod_destroy", None, [_H]),
+    # AGC bank
+    ("sdrgpu_agc_create", c_int, [c_int, c_int, POINTER(AgcDesignC), c_size_t, _PH]),
+    ("sdrgpu_agc_set_design", c_int, [_H, POINTER(AgcDesignC)]),
+    ("sdrgpu_agc_get_design", c_int, [_H, POINTER(AgcDesignC)]),
+    ("sdrgpu_agc_get_gains", c_int, [_H, c_void_p]),
+    ("sdrgpu_agc_last_plan", c_int, [_H, POINTER(c_int), POINTER(c_int)]),
+    ("sdrgpu_agc_set_stream", c_int, [_H, c_void_p]),
+    ("sdrgpu_agc_get_stream", c_int, [_H, _PH]),
+    ("sdrgpu_agc_output_len", c_int, [_H, c_size_t, _PS]),
+    ("sdrgpu_agc_process", c_int, [_H, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
+    ("sdrgpu_agc_process_dev", c_int, [_H, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
+    ("sdrgpu_agc_sync", c_int, [_H]),
+    ("sdrgpu_agc_reset", c_int, [_H]),
+    ("sdrgpu_agc_clone", c_int, [_H, _PH]),
+    ("sdrgpu_agc_destroy", None, [_H]),
     # FFT
     ("sdrgpu_fft_plan", c_int, [c_int, c_size_t, _PH]),
     ("sdrgpu_fft_set_stream", c_int, [_H, c_void_p]),

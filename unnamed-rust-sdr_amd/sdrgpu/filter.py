@@ -652,6 +652,141 @@ class Demod:
         check(lib().sdrgpu_demod_sync(self._h), "sdrgpu_demod_sync")
 
 
+# ---------------------------------------------------------------------------- Agc
+class Agc:
+    """AGC bank (sdrgpu_agc): a gain loop over `nch` channel rows, c64 or f32, output of the same
+    kind.  The gain moves once per frame of `frame` samples (frames aligned to the stream index),
+    each operation one f32 IEEE operation:
+
+      y[m] = x[m] * g;  s += |x[m]|          (c64: sqrtf(xr*xr + xi*xi))
+      at a frame's end: d = reference - (s / frame) * g;  g += (d < 0 ? attack : decay) * d,
+      clamped to [min_gain, max_gain] (a NaN becomes min_gain);  s = 0
+
+    The reference has no such stage; include/sdrgpu.h is the definition.  State (gain, partial
+    frame sum, samples counted) carries across blocks, so any partition into blocks gives the same
+    bits; rows are independent.  frame = 1 is the classic per-sample loop: correct, but serial."""
+
+    FIELDS = ("reference", "attack", "decay", "min_gain", "max_gain", "initial_gain")
+
+    def __init__(self, reference: float = 1.0, attack: float = 0.1, decay: float = 0.01,
+                 min_gain: float = 1e-6, max_gain: float = 1e6, initial_gain: float = 1.0,
+                 frame: int = 256, nch: int = 1, sample_kind: int = C64, device: int = 0, _handle=None):
+        self.nch = int(nch)
+        self.frame = int(frame)
+        self.sample_kind = sample_kind
+        self.device = device
+        self._h = ctypes.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            if not 0 <= self.frame < 2 ** 32:
+                raise _lib.SdrGpuError(_lib.ERR_INVALID, "Agc: frame")
+            d = _lib.AgcDesignC(reference, attack, decay, min_gain, max_gain, initial_gain, self.frame)
+            check(lib().sdrgpu_agc_create(device, sample_kind, ctypes.byref(d), self.nch,
+                                          ctypes.byref(self._h)), "sdrgpu_agc_create")
+
+    def close(self):
+        if self._h:
+            lib().sdrgpu_agc_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def design(self) -> dict:
+        d = _lib.AgcDesignC()
+        check(lib().sdrgpu_agc_get_design(self._h, ctypes.byref(d)), "sdrgpu_agc_get_design")
+        out = {k: getattr(d, k) for k in self.FIELDS}
+        out["frame"] = d.frame
+        return out
+
+    def set_design(self, **fields):
+        """Replaces the named fields (any of reference, attack, decay, min_gain, max_gain,
+        initial_gain; not frame) from the next process call on, ordered after the calls enqueued
+        before it; the state is kept."""
+        cur = self.design
+        for k in fields:
+            if k not in self.FIELDS:
+                raise _lib.SdrGpuError(_lib.ERR_INVALID, f"Agc.set_design: {k}")
+        cur.update(fields)
+        d = _lib.AgcDesignC(*(cur[k] for k in self.FIELDS), cur["frame"])
+        check(lib().sdrgpu_agc_set_design(self._h, ctypes.byref(d)), "sdrgpu_agc_set_design")
+
+    def gains(self) -> np.ndarray:
+        """The nch current gains, after everything enqueued on the handle's stream: reference /
+        gains()[r] is row r's level."""
+        g = np.empty(self.nch, np.float32)
+        check(lib().sdrgpu_agc_get_gains(self._h, g.ctypes.data), "sdrgpu_agc_get_gains")
+        return g
+
+    def last_plan(self):
+        """(form, copied) of the most recent non-empty call: form one of _lib.AGC_SHORT, AGC_LDS,
+        AGC_STREAM (-1 before the first call), copied whether the input was copied first."""
+        f, c = ctypes.c_int(), ctypes.c_int()
+        check(lib().sdrgpu_agc_last_plan(self._h, ctypes.byref(f), ctypes.byref(c)), "sdrgpu_agc_last_plan")
+        return f.value, bool(c.value)
+
+    def clone(self) -> "Agc":
+        h = ctypes.c_void_p()
+        check(lib().sdrgpu_agc_clone(self._h, ctypes.byref(h)), "sdrgpu_agc_clone")
+        return Agc(frame=self.frame, nch=self.nch, sample_kind=self.sample_kind, device=self.device, _handle=h)
+
+    def reset(self):
+        check(lib().sdrgpu_agc_reset(self._h), "sdrgpu_agc_reset")
+
+    def set_stream(self, stream_ptr: Optional[int]):
+        check(lib().sdrgpu_agc_set_stream(self._h, stream_ptr), "sdrgpu_agc_set_stream")
+
+    def stream(self) -> int:
+        s = ctypes.c_void_p()
+        check(lib().sdrgpu_agc_get_stream(self._h, ctypes.byref(s)), "sdrgpu_agc_get_stream")
+        return s.value or 0
+
+    def output_len(self, n_in: int) -> int:
+        n = ctypes.c_size_t()
+        check(lib().sdrgpu_agc_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
+        return n.value
+
+    def process(self, x, want_gain: bool = False):
+        """x: (n,) for nch = 1, else (nch, n) host samples -> y of x's shape and kind; with
+        want_gain, (y, gain) where gain is float32 of the same shape: the gain each sample was
+        scaled with."""
+        x = _as_c(x, self.sample_kind)
+        flat = self.nch == 1 and x.ndim == 1
+        if flat:
+            x = x.reshape(1, -1)
+        if x.ndim != 2 or x.shape[0] != self.nch:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Agc.process: shape must be (nch, n)")
+        n = x.shape[1]
+        out = np.empty((self.nch, max(n, 1)), dtype=x.dtype)
+        gain = np.empty((self.nch, max(n, 1)), dtype=np.float32) if want_gain else None
+        check(lib().sdrgpu_agc_process(self._h, x.ctypes.data, n, n, out.ctypes.data, out.shape[1],
+                                       gain.ctypes.data if want_gain else None, out.shape[1]),
+              "sdrgpu_agc_process")
+        y = out[:, :n]
+        y = y[0] if flat else y
+        if not want_gain:
+            return y
+        g = gain[:, :n]
+        return y, (g[0] if flat else g)
+
+    def process_dev(self, d_in_ptr: int, ld_in: int, n: int, d_out_ptr: int, ld_out: int,
+                    d_gain_ptr: Optional[int] = None, ld_gain: int = 0) -> int:
+        """Enqueue on the handle's stream with device pointers; row r is read at d_in + r*ld_in
+        samples, written at d_out + r*ld_out samples and, with d_gain_ptr, at d_gain + r*ld_gain
+        floats.  Returns n."""
+        check(lib().sdrgpu_agc_process_dev(self._h, d_in_ptr, ld_in, n, d_out_ptr, ld_out, d_gain_ptr, ld_gain),
+              "sdrgpu_agc_process_dev")
+        return n
+
+    def sync(self):
+        check(lib().sdrgpu_agc_sync(self._h), "sdrgpu_agc_sync")
+
+
 # ---------------------------------------------------------------------------- Upconverter
 class Upconverter:
     """Up-converter bank (digital up-converter, sdrgpu_upconv): K rows of c64 frames onto any

@@ -204,6 +204,29 @@ class Signal:
         rate (gain = rate / (2 pi deviation), sdrgpu_demod_fm_gain)."""
         return self.demod(_lib.DEMOD_FM, _filter.demod_fm_gain(self._rate, deviation))
 
+    def agc(self, reference: float = 1.0, attack: float = 0.1, decay: float = 0.01,
+            min_gain: float = 1e-6, max_gain: float = 1e6, initial_gain: float = 1.0,
+            frame: int = 256) -> "Signal":
+        """A frame-rate gain loop on a c64 or f32 Signal (filter.Agc with one row): the same kind
+        and rate, levelled towards `reference`."""
+        sk = self.sample_kind
+        if sk == _lib.CU8:
+            raise _lib.SdrGpuError(_lib.ERR_UNSUPPORTED, "agc: CU8 samples")
+        src = self
+
+        def gen():
+            a = None
+            for b in src.blocks():
+                b = np.asarray(b).reshape(-1)
+                if a is None:
+                    kind = sk if sk is not None else (_lib.C64 if np.iscomplexobj(b) else _lib.F32)
+                    a = _filter.Agc(reference, attack, decay, min_gain, max_gain, initial_gain, frame, 1,
+                                    sample_kind=kind)
+                y = a.process(b)
+                if y.size:
+                    yield y
+        return Signal(self._rate, gen, sk)
+
     def resample(self, rate: float) -> "Signal":
         """Signal::resample (src/signal/mod.rs:78-84): SincBestQuality (this library's own
         sinc table)."""
