@@ -751,6 +751,87 @@ int sdrgpu_stft_reset(sdrgpu_stft* h);
 void sdrgpu_stft_destroy(sdrgpu_stft* h);
 
 /* =====================================================================================
+ * Inverse FFT and streaming ISTFT: spectrum frames back into one stream.
+ * No reference counterpart (the reference has no inverse); this is the way back from
+ * sdrgpu_fft_exec and sdrgpu_stft_process, as sdrgpu_synth is from sdrgpu_chan.
+ * Let h = n / 2 (integer division).  A spectrum frame is n C64 values
+ *   F[i] = X[(i - h) mod n] / sqrt(n),
+ * what sdrgpu_fft_exec and the STFT store in complex mode.
+ * Inverse frame, t = 0 .. n-1:
+ *   y[t] = (1/sqrt(n)) * sum_i F[i] * exp(+2*pi*i * ((i - h) mod n) * t / n),
+ * so if F is the forward call's output for a frame x, y = x.
+ * sdrgpu_ifft_exec turns `count` collated frames into count * n samples on the plan handle
+ * (what it needs is made by the first inverse call and lives in the handle).  It is the ISTFT
+ * below at hop n with the all-ones window, restarted at every call.  SDRGPU_FFT_OUT_DB does
+ * not apply to it: on a handle set to dB output the inverse calls return SDRGPU_ERR_INVALID.
+ * ISTFT: a handle has n, a hop H with 1 <= H <= n and a real synthesis window w[0..n) (NULL:
+ * all ones).  Frames are counted j = 0, 1, ... from create or reset, across calls; after c
+ * frames in total the handle has emitted exactly c * H samples, and
+ *   out[u] = sum over j >= 0 with 0 <= u - j*H < n, j ascending, of w[u - j*H] * y_j[u - j*H].
+ * Under the STFT's framing frame j covers stream samples [(j+1)H - n, (j+1)H), so out[u] is
+ * stream sample u - (n - H): the latency is n - H samples, the zero prefill the Window adapter
+ * put in front of the stream.
+ * sdrgpu_istft_window (host only) writes the COLA synthesis window of an analysis window a
+ * (NULL: ones):  out[i] = a[i] / sum_{m in Z, 0 <= i + m*hop < n} a[i + m*hop]^2, in f64, rounded
+ * once; SDRGPU_ERR_INVALID where a denominator is zero (or n == 0, hop == 0, hop > n).  With
+ * analysis = NULL it is the window for which the ISTFT of sdrgpu_stft's frames is the stream
+ * delayed by n - hop.
+ * How it is computed: the handle's forward plan transforms each spectrum frame
+ * into C_j (collated, scaled by 1/sqrt(n)), and y_j[t] = exp(-2*pi*i*h*t/n) * C_j[(h - t) mod n]
+ * exactly; out[u] is the ascending-j sum of c[t] * C_j[(h - t) mod n], each term one fused
+ * complex multiply-add, with c[t] = w[t] * exp(-2*pi*i*h*t/n) one table made on the host in f64
+ * and rounded once.  The 1/sqrt(n) is the forward plan's own scale; it is not folded into c.
+ * Partitions: every output sample is the same operations in the same order wherever the frame
+ * stream is cut, so any partition into calls, calls of 0 frames included, is bit-identical; a
+ * clone continues from the same state with identical bits and gets its own stream; reset
+ * returns to frame 0.  A non-finite value in frame j reaches only the outputs [j*H, j*H + n).
+ * In place: an output range that overlaps the input runs on a device copy of the input, as in
+ * sdrgpu_fft_exec_dev.  Long calls run in batches bounded by a device slab; sdrgpu_istft_set_batch
+ * sets the batch size in frames (0: automatic) and is allowed only while no frame has been taken
+ * since create or reset (else SDRGPU_ERR_INVALID).  It changes no output bit; it exists so that
+ * tests can cut batches at small sizes.
+ * Limits, checked before the device is looked at: a null handle or out-pointer, n == 0,
+ * hop == 0, hop > n: SDRGPU_ERR_INVALID; n > 2^24: SDRGPU_ERR_UNSUPPORTED, as sdrgpu_fft_plan;
+ * n_frames * hop > out_cap: SDRGPU_ERR_OUTPUT_CAP with *n_out set and nothing enqueued;
+ * n_frames == 0: SDRGPU_OK with *n_out = 0.  The handle keeps ceil(n/hop) - 1 transformed
+ * frames on the device in front of a batch: hop = 1 at n = 4096 is 128 MiB, and a create whose
+ * ring does not fit returns SDRGPU_ERR_NOMEM.
+ * ===================================================================================== */
+int sdrgpu_ifft_exec(sdrgpu_fft* h, const void* in, void* out, size_t count);
+int sdrgpu_ifft_exec_dev(sdrgpu_fft* h, const void* d_in, void* d_out, size_t count);
+
+typedef struct sdrgpu_istft sdrgpu_istft;
+
+int sdrgpu_istft_window(size_t n, size_t hop, const float* analysis, float* out);
+int sdrgpu_istft_create(int device, size_t n, size_t hop, const float* window, sdrgpu_istft** out);
+int sdrgpu_istft_set_batch(sdrgpu_istft* h, size_t frames);
+/* Which kernels run the handle.  SDRGPU_ISTFT_GENERAL, every shape: the forward
+ * plan per frame, then an overlap-add gather, as described above.  SDRGPU_ISTFT_TILE, n a power
+ * of two 2 .. 4096, any hop: one fused launch per call (contiguous frame loads, inverse LDS-tile
+ * FFT, overlap-add in registers); its window table is w[t] / sqrt(n), rounded once, so its bits
+ * differ from the general route's in the last places.  SDRGPU_ISTFT_AUTO (the default) takes the
+ * tile route only for the shapes where it measured faster; as measured so far that is none
+ * (profiles/istft_ab.txt), so AUTO is the general route.  Like set_batch, allowed only while
+ * no frame has been taken since create or reset, so a stream never changes route; a route the
+ * shape does not have is SDRGPU_ERR_UNSUPPORTED.  get_route reports the route in use (GENERAL or
+ * TILE).  Both routes keep every promise above.  Introspection and a switch for tests and
+ * benches, like sdrgpu_fir_set_algorithm. */
+enum sdrgpu_istft_route { SDRGPU_ISTFT_AUTO = 0, SDRGPU_ISTFT_GENERAL = 1, SDRGPU_ISTFT_TILE = 2 };
+int sdrgpu_istft_set_route(sdrgpu_istft* h, int route);
+int sdrgpu_istft_get_route(const sdrgpu_istft* h, int* route);
+int sdrgpu_istft_set_stream(sdrgpu_istft* h, void* hip_stream);
+int sdrgpu_istft_get_stream(const sdrgpu_istft* h, void** hip_stream);
+int sdrgpu_istft_output_len(const sdrgpu_istft* h, size_t n_frames, size_t* n_out);
+int sdrgpu_istft_process(sdrgpu_istft* h, const void* in, size_t n_frames, void* out,
+                         size_t out_cap, size_t* n_out);
+int sdrgpu_istft_process_dev(sdrgpu_istft* h, const void* d_in, size_t n_frames, void* d_out,
+                             size_t out_cap, size_t* n_out);
+int sdrgpu_istft_sync(sdrgpu_istft* h);
+int sdrgpu_istft_reset(sdrgpu_istft* h);
+int sdrgpu_istft_clone(const sdrgpu_istft* h, sdrgpu_istft** out);
+void sdrgpu_istft_destroy(sdrgpu_istft* h);
+
+/* =====================================================================================
  * Biquad designs and batched PLL.
  * Replaces: BiquadD::design (src/filter/biquad.rs:73-155), Biquad::new/apply (:25-56),
  *           filter::Identity (src/filter/simple.rs:3-19),

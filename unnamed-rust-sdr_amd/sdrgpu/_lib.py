@@ -42,6 +42,10 @@ FIR_KERNEL_CU8_CONVERTED = 16
 FFT_OUT_COMPLEX = 0
 FFT_OUT_DB = 1
 
+ISTFT_AUTO = 0
+ISTFT_GENERAL = 1
+ISTFT_TILE = 2
+
 PLL_OUT_FILTER = 0
 PLL_OUT_STEREO_DIFF = 1
 
@@ -283,6 +287,23 @@ SIGNATURES = [
     ("sdrgpu_stft_sync", c_int, [_H]),
     ("sdrgpu_stft_reset", c_int, [_H]),
     ("sdrgpu_stft_destroy", None, [_H]),
+    # inverse FFT, ISTFT
+    ("sdrgpu_ifft_exec", c_int, [_H, c_void_p, c_void_p, c_size_t]),
+    ("sdrgpu_ifft_exec_dev", c_int, [_H, c_void_p, c_void_p, c_size_t]),
+    ("sdrgpu_istft_window", c_int, [c_size_t, c_size_t, c_void_p, c_void_p]),
+    ("sdrgpu_istft_create", c_int, [c_int, c_size_t, c_size_t, c_void_p, _PH]),
+    ("sdrgpu_istft_set_batch", c_int, [_H, c_size_t]),
+    ("sdrgpu_istft_set_route", c_int, [_H, c_int]),
+    ("sdrgpu_istft_get_route", c_int, [_H, POINTER(c_int)]),
+    ("sdrgpu_istft_set_stream", c_int, [_H, c_void_p]),
+    ("sdrgpu_istft_get_stream", c_int, [_H, _PH]),
+    ("sdrgpu_istft_output_len", c_int, [_H, c_size_t, _PS]),
+    ("sdrgpu_istft_process", c_int, [_H, c_void_p, c_size_t, c_void_p, c_size_t, _PS]),
+    ("sdrgpu_istft_process_dev", c_int, [_H, c_void_p, c_size_t, c_void_p, c_size_t, _PS]),
+    ("sdrgpu_istft_sync", c_int, [_H]),
+    ("sdrgpu_istft_reset", c_int, [_H]),
+    ("sdrgpu_istft_clone", c_int, [_H, _PH]),
+    ("sdrgpu_istft_destroy", None, [_H]),
     # PLL
     ("sdrgpu_pll_create", c_int, [c_int, POINTER(PllParamsC), c_size_t, _PH]),
     ("sdrgpu_pll_set_output_mode", c_int, [_H, c_int]),

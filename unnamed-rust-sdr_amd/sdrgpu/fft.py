@@ -8,6 +8,8 @@ values are the collated, 1/sqrt(N)-normalised spectrum exactly as the reference 
 `Stft` is the streaming composition sig.window(N/rate).decimate(rate/hop).map(fft::fft)
 (examples/live.rs:29-39).  Any N >= 1 plans, like rustfft (fft.rs:10-11): powers of two on
 the Stockham / four-step kernels, other lengths on mixed-radix tiles or Bluestein.
+The way back has no reference counterpart (include/sdrgpu.h defines it): `FftPlan.inverse` /
+`ifft` undo `exec` / `fft`, and `Istft` overlap-adds the frames of an `Stft` into one stream.
 """
 from __future__ import annotations
 
@@ -97,6 +99,20 @@ class FftPlan:
     def sync(self):
         check(lib().sdrgpu_fft_sync(self._h), "sdrgpu_fft_sync")
 
+    def inverse(self, x) -> np.ndarray:
+        """x: (count, n) or (n,) collated spectra (what exec returns) -> the frames' samples, same
+        shape.  Not for output='db' plans."""
+        x = np.ascontiguousarray(x, np.complex64)
+        squeeze = x.ndim == 1
+        x2 = x.reshape(-1, self.n)
+        out = np.empty(x2.shape, np.complex64)
+        check(lib().sdrgpu_ifft_exec(self._h, x2.ctypes.data, out.ctypes.data, x2.shape[0]),
+              "sdrgpu_ifft_exec")
+        return out[0] if squeeze else out
+
+    def inverse_dev(self, d_in: int, d_out: int, count: int):
+        check(lib().sdrgpu_ifft_exec_dev(self._h, d_in, d_out, count), "sdrgpu_ifft_exec_dev")
+
 
 def fft(x, rate: float, device: int = 0):
     """fft::fft (fft.rs:3-28) of one finite complex signal: (freqs, values)."""
@@ -110,6 +126,24 @@ def rfft(x, rate: float, device: int = 0):
     x = np.ascontiguousarray(x, np.float32)
     p = FftPlan(x.size, device)
     return freqs(x.size, rate)[x.size // 2:], p.exec_real(x)
+
+
+def ifft(values, device: int = 0) -> np.ndarray:
+    """The signal whose fft(...) values are `values`: one collated, 1/sqrt(N)-scaled spectrum."""
+    v = np.ascontiguousarray(values, np.complex64).reshape(-1)
+    return FftPlan(v.size, device).inverse(v)
+
+
+def istft_window(n: int, hop: int, analysis=None) -> np.ndarray:
+    """COLA synthesis window of an analysis window (None: ones): a[i] / sum_m a[i + m*hop]^2.
+    With analysis=None, Istft(n, hop, it) after Stft(n, hop) returns the stream delayed by n - hop."""
+    a = None if analysis is None else np.ascontiguousarray(analysis, np.float32)
+    if a is not None and a.shape != (int(n),):
+        raise _lib.SdrGpuError(_lib.ERR_INVALID, "analysis window must have n entries")
+    out = np.empty(int(n), np.float32)
+    check(lib().sdrgpu_istft_window(int(n), int(hop), None if a is None else a.ctypes.data,
+                                    out.ctypes.data), "sdrgpu_istft_window")
+    return out
 
 
 class Stft:
@@ -190,3 +224,96 @@ class Stft:
 
     def sync(self):
         check(lib().sdrgpu_stft_sync(self._h), "sdrgpu_stft_sync")
+
+    def inverse(self, window="cola") -> "Istft":
+        """The matching Istft (same n, hop, device): with window='cola' its output for this handle's
+        complex frames is the input stream delayed by n - hop."""
+        return Istft(self.n, self.hop, window, self.device)
+
+
+class Istft:
+    """Streaming inverse of Stft: collated spectrum frames (n values each) back into one stream by
+    windowed overlap-add, hop samples out per frame; sample u of the output is stream sample
+    u - (n - hop) of the Stft's input.  window: 'cola' (istft_window(n, hop)), None (ones) or n reals."""
+
+    def __init__(self, n: int, hop: int, window="cola", device: int = 0, _handle=None):
+        self.n, self.hop, self.device = int(n), int(hop), device
+        if isinstance(window, str):
+            if window != "cola":
+                raise _lib.SdrGpuError(_lib.ERR_INVALID, "window must be 'cola', None or an array")
+            window = istft_window(self.n, self.hop)
+        self.window = None if window is None else np.ascontiguousarray(window, np.float32)
+        if self.window is not None and self.window.shape != (self.n,):
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "window must have n entries")
+        self._h = ctypes.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+            return
+        w = None if self.window is None else self.window.ctypes.data
+        check(lib().sdrgpu_istft_create(device, self.n, self.hop, w, ctypes.byref(self._h)),
+              "sdrgpu_istft_create")
+
+    def close(self):
+        if self._h:
+            lib().sdrgpu_istft_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr: Optional[int]):
+        check(lib().sdrgpu_istft_set_stream(self._h, stream_ptr), "sdrgpu_istft_set_stream")
+
+    def stream(self) -> int:
+        s = ctypes.c_void_p()
+        check(lib().sdrgpu_istft_get_stream(self._h, ctypes.byref(s)), "get_stream")
+        return s.value or 0
+
+    def set_batch(self, frames: int):
+        """Frames per internal batch (0: automatic); only before the first frame or after reset.
+        Changes no output bit (tests cut batches small with it)."""
+        check(lib().sdrgpu_istft_set_batch(self._h, int(frames)), "sdrgpu_istft_set_batch")
+
+    def set_route(self, route: int):
+        """_lib.ISTFT_AUTO / ISTFT_GENERAL / ISTFT_TILE; only before the first frame or after reset."""
+        check(lib().sdrgpu_istft_set_route(self._h, int(route)), "sdrgpu_istft_set_route")
+
+    def route(self) -> int:
+        r = ctypes.c_int()
+        check(lib().sdrgpu_istft_get_route(self._h, ctypes.byref(r)), "sdrgpu_istft_get_route")
+        return r.value
+
+    def output_len(self, n_frames: int) -> int:
+        n = ctypes.c_size_t()
+        check(lib().sdrgpu_istft_output_len(self._h, n_frames, ctypes.byref(n)), "output_len")
+        return n.value
+
+    def process(self, frames) -> np.ndarray:
+        """frames: (count, n) or (n,) collated spectra -> count * hop samples."""
+        x = np.ascontiguousarray(frames, np.complex64).reshape(-1, self.n)
+        nf = x.shape[0]
+        out = np.empty(max(nf * self.hop, 1), np.complex64)
+        got = ctypes.c_size_t()
+        check(lib().sdrgpu_istft_process(self._h, x.ctypes.data, nf, out.ctypes.data, nf * self.hop,
+                                         ctypes.byref(got)), "sdrgpu_istft_process")
+        return out[:got.value]
+
+    def process_dev(self, d_in: int, n_frames: int, d_out: int, out_cap: int) -> int:
+        got = ctypes.c_size_t()
+        check(lib().sdrgpu_istft_process_dev(self._h, d_in, n_frames, d_out, out_cap,
+                                             ctypes.byref(got)), "sdrgpu_istft_process_dev")
+        return got.value
+
+    def reset(self):
+        check(lib().sdrgpu_istft_reset(self._h), "sdrgpu_istft_reset")
+
+    def clone(self) -> "Istft":
+        h = ctypes.c_void_p()
+        check(lib().sdrgpu_istft_clone(self._h, ctypes.byref(h)), "sdrgpu_istft_clone")
+        return Istft(self.n, self.hop, self.window, self.device, _handle=h)
+
+    def sync(self):
+        check(lib().sdrgpu_istft_sync(self._h), "sdrgpu_istft_sync")
