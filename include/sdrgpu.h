@@ -84,6 +84,10 @@ enum sdrgpu_fir_algo {
                                      a sample more than 2^29 below the largest sample of its
                                      1024-sample tile is resolved to 2^-38 of that sample, not
                                      to its own level (DIRECT keeps f32's range per sample). */
+    SDRGPU_FIR_FAST_CONV = 4,     /* overlap-save on blocks of 2^13 .. 2^20 points through a
+                                     four-step FFT over a scratch slab: c64 (and rtl_tcp u8)
+                                     samples, 2 <= ntaps <= 2^19 + 1, any decim; see "Long
+                                     filters" in the FIR section below. */
 };
 
 /* Which kernel ran the most recent block (sdrgpu_fir_last_kernel; test / bench introspection,
@@ -96,6 +100,7 @@ enum sdrgpu_fir_kernel {
     SDRGPU_FIR_KERNEL_BF16X3 = 3,        /* fir_mfma: register-fed exact bf16 x3 MFMA */
     SDRGPU_FIR_KERNEL_OVERLAP_SAVE = 4,
     SDRGPU_FIR_KERNEL_DIRECT = 5,
+    SDRGPU_FIR_KERNEL_FAST_CONV = 6,     /* fir_fc: three tile-FFT passes over a scratch slab */
     SDRGPU_FIR_KERNEL_CU8_CONVERTED = 16  /* flag */
 };
 
@@ -146,12 +151,56 @@ int sdrgpu_event_destroy(void* event);
  * MFMA path at 2 input bytes per sample); history and outputs are C64.
  * (F32 samples with C64 taps do not type-check in the reference: f32 is not
  * Mul<Complex<f32>, Output=f32>.)
+ *
+ * Long filters (SDRGPU_FIR_FAST_CONV).  Past the MFMA kernels (ntaps <= 257 .. 273) and the
+ * one-tile overlap-save (about ntaps <= 1025, decim in {1, 2, 4, 8}) the direct form costs
+ * ntaps / decim multiply-adds per input sample.  Fast convolution is overlap-save on blocks of N
+ * points, N a power of two in [2^13, 2^20] with N >= 2 (ntaps - 1): three launches per batch of
+ * blocks (forward transform in two passes over a scratch slab of at most 256 MiB, the product with
+ * the filter's spectrum and the way back fused into the second), same definition, same state, any
+ * partition of the stream.  Limits: c64 or rtl_tcp u8 samples (u8 through the conversion step, so
+ * the kernel reads SDRGPU_FIR_KERNEL_FAST_CONV | _CU8_CONVERTED), f32 or c64 taps, any decim,
+ * 2 <= ntaps <= 2^19 + 1; f32 samples and longer filters stay on the direct form, and
+ * sdrgpu_fir_set_algorithm(SDRGPU_FIR_FAST_CONV) returns SDRGPU_ERR_UNSUPPORTED for them.
+ * N is chosen automatically as the smallest block with N >= 4 (ntaps - 1) (2^20 at the most), or
+ * forced with sdrgpu_fir_set_conv_block (0: automatic again; a size that is no power of two in
+ * range or is below 2 (ntaps - 1): SDRGPU_ERR_INVALID; it takes effect at the next block and
+ * changes results only within the accuracy below).  sdrgpu_fir_conv_plan is the handle-free
+ * bookkeeping: the block N = m1 * m2 of (ntaps, decim, block) and the stream positions `valid` a
+ * block yields, a multiple of decim wherever decim <= N - (ntaps - 1).
+ * Accuracy: the spectrum and the twiddles are made in f64 and rounded once; against an f64
+ * convolution of the same f32 data the outputs are within 1e-5 of the output's RMS (largest error)
+ * and 1e-5 relative (l2) at every block size (measured per N: DESIGN.md 3.2a).  The reference's own
+ * f32 sequential sum is further than that from the f64 result for long filters (2.1e-5 at 32769
+ * taps), so this path is nearer the exact convolution than the direct form there, and bits differ
+ * between partitions of a stream, as for overlap-save.
+ * Cost of inf / NaN samples: a block's transform mixes all of its samples, so one non-finite sample
+ * makes every output of its block (and of the next, through the ntaps - 1 overlap) take the
+ * per-output sequential sum: up to `valid` * ntaps products per block instead of a transform.
+ * Measured at 4096 taps, decim 1, 2^22 samples per call: 0.095 ms finite, 3.98 ms with one NaN per
+ * 2^20 samples (about 1 ms per non-finite sample), 16.7 ms all NaN (176 times; the direct form
+ * takes 3.6 ms for 2^24 finite samples through that filter).  A stream that carries such samples
+ * routinely can be forced onto SDRGPU_FIR_DIRECT.
+ * SDRGPU_FIR_AUTO tries this path after overlap-save and before the direct form, per block: it is
+ * taken for finite taps where ntaps >= 1026, the call has at least 256 samples and
+ * (kept outputs * ntaps) >= 2 * (blocks * N), so a short call of a long filter stays on the direct
+ * form.  Those are the edges of the measured grid, not crossovers: against the direct form the
+ * path was faster on every measured row (ntaps 1026 .. 2^19 + 1, decim 1, 4, 16, calls of 2^8 ..
+ * 2^24 samples; 2^24 samples at 16384 taps, decim 1: 0.33 ms against 290 ms).
  * ===================================================================================== */
 typedef struct sdrgpu_fir sdrgpu_fir;
 
 int sdrgpu_fir_create(int device, int sample_kind, int tap_kind, const void* taps,
                       size_t ntaps, uint32_t decim, sdrgpu_fir** out);
 int sdrgpu_fir_set_algorithm(sdrgpu_fir* h, int algo);
+/* Block size of SDRGPU_FIR_FAST_CONV ("Long filters" above): 0 automatic. */
+int sdrgpu_fir_set_conv_block(sdrgpu_fir* h, size_t n);
+int sdrgpu_fir_get_conv_block(const sdrgpu_fir* h, size_t* n);
+/* Pure host function: SDRGPU_ERR_UNSUPPORTED for ntaps < 2 or ntaps > 2^19 + 1,
+ * SDRGPU_ERR_INVALID for ntaps == 0, decim == 0 or a block the handle would refuse.  Any of the
+ * four outputs may be NULL. */
+int sdrgpu_fir_conv_plan(size_t ntaps, uint32_t decim, size_t block, size_t* n, size_t* m1,
+                         size_t* m2, size_t* valid);
 /* Use an external hipStream_t (NULL restores the handle's own stream). */
 int sdrgpu_fir_set_stream(sdrgpu_fir* h, void* hip_stream);
 int sdrgpu_fir_get_stream(const sdrgpu_fir* h, void** hip_stream);
@@ -176,7 +225,7 @@ int sdrgpu_fir_process_dev(sdrgpu_fir* h, const void* d_in, size_t n_in, void* d
 int sdrgpu_fir_process_async(sdrgpu_fir* h, const void* in, size_t n_in, void* out,
                              size_t out_cap, size_t* n_out);
 int sdrgpu_fir_sync(sdrgpu_fir* h);
-/* The algorithm (SDRGPU_FIR_DIRECT / _OVERLAP_SAVE / _MATRIX) that ran the most recent
+/* The algorithm (SDRGPU_FIR_DIRECT / _OVERLAP_SAVE / _MATRIX / _FAST_CONV) that ran the most recent
  * non-empty block; SDRGPU_FIR_AUTO before the first one.  Introspection for tests and
  * benches (which kernel family a shape actually took); no reference counterpart. */
 int sdrgpu_fir_last_algorithm(const sdrgpu_fir* h, int* algo);
@@ -193,6 +242,8 @@ typedef struct sdrgpu_firbank sdrgpu_firbank;
 int sdrgpu_firbank_create(int device, int sample_kind, int tap_kind, const void* taps,
                           size_t ntaps, uint32_t decim, size_t nch, sdrgpu_firbank** out);
 int sdrgpu_firbank_set_algorithm(sdrgpu_firbank* h, int algo);
+int sdrgpu_firbank_set_conv_block(sdrgpu_firbank* h, size_t n);  /* as sdrgpu_fir_set_conv_block */
+int sdrgpu_firbank_get_conv_block(const sdrgpu_firbank* h, size_t* n);
 int sdrgpu_firbank_set_stream(sdrgpu_firbank* h, void* hip_stream);
 int sdrgpu_firbank_get_stream(const sdrgpu_firbank* h, void** hip_stream);
 int sdrgpu_firbank_output_len(const sdrgpu_firbank* h, size_t n_in, size_t* n_out);

@@ -7,6 +7,7 @@
 // filters a block is FirPaths' business (fir_select.cpp).
 #include <vector>
 
+#include "fir_fc_plan.hpp"
 #include "fir_select.hpp"
 
 using namespace sdrgpu;
@@ -199,6 +200,7 @@ struct FirCore {
         if (st) return st;
         DeviceGuard g(device);
         (void)dst->paths.set_algorithm(paths.algorithm());  // same shape: accepted again
+        (void)dst->paths.set_conv_block(paths.conv_block());
         dst->seen = seen;
         dst->cur = 0;
         if (K > 1) {
@@ -232,6 +234,16 @@ int clone(const H* h, H** out) {
 
 int set_algorithm(FirCore* c, int algo) {
     return c ? c->paths.set_algorithm(algo) : SDRGPU_ERR_INVALID;
+}
+
+int set_conv_block(FirCore* c, size_t n) {
+    return c ? c->paths.set_conv_block(n) : SDRGPU_ERR_INVALID;
+}
+
+int get_conv_block(const FirCore* c, size_t* n) {
+    if (!c || !n) return SDRGPU_ERR_INVALID;
+    *n = c->paths.conv_block();
+    return SDRGPU_OK;
 }
 
 int set_stream(FirCore* c, void* s) {
@@ -276,6 +288,24 @@ void sdrgpu_firbank_destroy(sdrgpu_firbank* h) { destroy_handle(h); }
 
 int sdrgpu_fir_set_algorithm(sdrgpu_fir* h, int algo) { return set_algorithm(h, algo); }
 int sdrgpu_firbank_set_algorithm(sdrgpu_firbank* h, int algo) { return set_algorithm(h, algo); }
+
+int sdrgpu_fir_set_conv_block(sdrgpu_fir* h, size_t n) { return set_conv_block(h, n); }
+int sdrgpu_firbank_set_conv_block(sdrgpu_firbank* h, size_t n) { return set_conv_block(h, n); }
+int sdrgpu_fir_get_conv_block(const sdrgpu_fir* h, size_t* n) { return get_conv_block(h, n); }
+int sdrgpu_firbank_get_conv_block(const sdrgpu_firbank* h, size_t* n) { return get_conv_block(h, n); }
+
+int sdrgpu_fir_conv_plan(size_t ntaps, uint32_t decim, size_t block, size_t* n, size_t* m1,
+                         size_t* m2, size_t* valid) {
+    if (ntaps == 0 || decim == 0) return SDRGPU_ERR_INVALID;
+    if (ntaps < 2 || ntaps > firfc::kMaxTaps) return SDRGPU_ERR_UNSUPPORTED;
+    firfc::Plan p;
+    if (!firfc::make_plan(ntaps, decim, block, &p)) return SDRGPU_ERR_INVALID;
+    if (n) *n = (size_t)p.N;
+    if (m1) *m1 = (size_t)p.M1;
+    if (m2) *m2 = (size_t)p.M2;
+    if (valid) *valid = (size_t)p.V;
+    return SDRGPU_OK;
+}
 
 int sdrgpu_fir_set_stream(sdrgpu_fir* h, void* s) { return set_stream(h, s); }
 int sdrgpu_firbank_set_stream(sdrgpu_firbank* h, void* s) { return set_stream(h, s); }

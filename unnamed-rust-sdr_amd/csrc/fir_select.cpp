@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <cmath>
 
+#include "fir_fc_plan.hpp"
+
 namespace sdrgpu {
 
 using detail::DeviceGuard;
@@ -24,6 +26,44 @@ bool FirPaths::mx_shape_ok() const {
 
 bool FirPaths::os_shape_ok() const {
     return fir_os_supported(sk == SDRGPU_CU8 ? SDRGPU_C64 : sk, tk, K, D) != 0;
+}
+
+bool FirPaths::fc_shape_ok() const {
+    return fir_fc_supported(sk == SDRGPU_CU8 ? SDRGPU_C64 : sk, K) != 0;
+}
+
+// SDRGPU_FIR_AUTO's rule for a block the MFMA and overlap-save kernels left (set
+// from profiles/fir_long_ab.txt): the direct form costs (kept outputs x K) products, fast convolution
+// (blocks x N) transformed points, and it is taken where the first is at least kAutoCost times the
+// second, for finite taps (a non-finite tap makes every output take the per-output recompute) of
+// at least kAutoMinTaps and calls of at least kAutoMinCall samples.  A short call of a long filter
+// therefore stays on the direct form.
+bool FirPaths::fc_auto_takes(const FirParams& p) {
+    if (!fc_shape_ok() || K < firfc::kAutoMinTaps || p.n_in < firfc::kAutoMinCall) return false;
+    firfc::Plan pl;
+    if (!firfc::make_plan((firfc::u64)K, (firfc::u64)D, fc_block, &pl)) return false;
+    const double direct = (double)p.n_out * (double)K;
+    const double conv = (double)firfc::call_blocks(pl, (firfc::u64)p.n_in, (firfc::u64)p.i0) * (double)pl.N;
+    if (!(direct >= firfc::kAutoCost * conv)) return false;
+    if (taps_finite < 0) {
+        const float* h = reinterpret_cast<const float*>(taps.data());
+        const size_t nf = (size_t)K * (tk == SDRGPU_C64 ? 2 : 1);
+        taps_finite = 1;
+        for (size_t i = 0; i < nf; ++i)
+            if (!std::isfinite(h[i])) taps_finite = 0;
+    }
+    return taps_finite == 1;
+}
+
+int FirPaths::set_conv_block(size_t n) {
+    if (n && !firfc::block_ok((firfc::u64)K, (firfc::u64)n)) return SDRGPU_ERR_INVALID;
+    if (n == fc_block) return SDRGPU_OK;
+    DeviceGuard g(device);
+    if (fc_state) fir_fc_release(fc_state);  // hipFree waits for the blocks that still read it
+    fc_state = nullptr;
+    fc_status = SDRGPU_OK;
+    fc_block = n;
+    return SDRGPU_OK;
 }
 
 int FirPaths::prepare(int dev, int sample_kind, int tap_kind, const void* h, int ntaps, int decim) {
@@ -47,12 +87,17 @@ void FirPaths::release() {
     if (os_state) fir_os_release(os_state);
     os_state = nullptr;
     stage_conv.release();
+    if (fc_state) fir_fc_release(fc_state);
+    fc_state = nullptr;
+    fc_status = SDRGPU_OK;
+    fc_slab.release();
 }
 
 int FirPaths::set_algorithm(int a) {
-    if (a < SDRGPU_FIR_AUTO || a > SDRGPU_FIR_MATRIX) return SDRGPU_ERR_INVALID;
+    if (a < SDRGPU_FIR_AUTO || a > SDRGPU_FIR_FAST_CONV) return SDRGPU_ERR_INVALID;
     if (a == SDRGPU_FIR_OVERLAP_SAVE && !os_shape_ok()) return SDRGPU_ERR_UNSUPPORTED;
     if (a == SDRGPU_FIR_MATRIX && !mx_shape_ok()) return SDRGPU_ERR_UNSUPPORTED;
+    if (a == SDRGPU_FIR_FAST_CONV && !fc_shape_ok()) return SDRGPU_ERR_UNSUPPORTED;
     algo = a;
     return SDRGPU_OK;
 }
@@ -138,7 +183,16 @@ int FirPaths::launch(FirParams& p, hipStream_t s, int* ran_algo, int* kernel) {
         if (st == SDRGPU_OK || algo == SDRGPU_FIR_OVERLAP_SAVE)
             return ran(SDRGPU_FIR_OVERLAP_SAVE, SDRGPU_FIR_KERNEL_OVERLAP_SAVE, st);
     }
-    // 7. direct form, every shape: fir_direct_launch (fir_direct.hip) takes the wave-private
+    if (algo == SDRGPU_FIR_FAST_CONV || (algo == SDRGPU_FIR_AUTO && fc_auto_takes(p))) {
+        // 7. fast convolution (c64 by now): forced, or where AUTO's rule says it wins; as for
+        // overlap-save, its failure is the answer only when it was forced
+        if (!fc_state && fc_status == SDRGPU_OK)
+            fc_state = fir_fc_prepare(tk, taps.data(), K, D, fc_block, &fc_status);
+        st = fc_state ? fir_fc_launch(p, fc_state, fc_slab, s) : fc_status;
+        if (st == SDRGPU_OK || algo == SDRGPU_FIR_FAST_CONV)
+            return ran(SDRGPU_FIR_FAST_CONV, SDRGPU_FIR_KERNEL_FAST_CONV, st);
+    }
+    // 8. direct form, every shape: fir_direct_launch (fir_direct.hip) takes the wave-private
     // direct2 kernel where fir_direct2_supported, else the R-blocked kernel (R = 8, then 2) while
     // its tile fits the LDS budget, else the naive kernel
     return ran(SDRGPU_FIR_DIRECT, SDRGPU_FIR_KERNEL_DIRECT, fir_direct_launch(p, s));

@@ -22,6 +22,15 @@ void* fir_os_prepare(int device, int sample_kind, int tap_kind, const void* taps
 int fir_os_launch(const FirParams& p, void* os_state, hipStream_t s);
 void fir_os_release(void* os_state);
 
+// Fast convolution for long filters (fir_fc.hip; the counting is fir_fc_plan.hpp): c64 samples,
+// 2 <= K <= 2^19 + 1, any D.  The state (plan, filter spectrum, twiddles) is built once per handle
+// and block size from the host taps; block: 0 automatic, else a size firfc::block_ok accepts.
+// `slab` is the caller's scratch for the blocks' transforms, grown on demand.
+int fir_fc_supported(int sample_kind, int K);
+void* fir_fc_prepare(int tap_kind, const void* taps, int K, int D, size_t block, int* status);
+int fir_fc_launch(const FirParams& p, void* fc_state, detail::DevBuf& slab, hipStream_t s);
+void fir_fc_release(void* fc_state);
+
 // rtl_tcp bytes -> c64 (ingest.hip): nch rows of n samples, dense output rows.
 int cu8_to_c64_launch(const void* in, long ld_in, long n, long nch, void* out, hipStream_t s);
 
@@ -33,6 +42,10 @@ struct FirPaths {
     // SDRGPU_ERR_UNSUPPORTED when no kernel of the forced algorithm covers the shape
     int set_algorithm(int algo);
     int algorithm() const { return algo; }
+    // block size of the fast-convolution path: 0 automatic; SDRGPU_ERR_INVALID for a size that is
+    // no power of two in [2^13, 2^20] or is below 2 (K - 1).  Takes effect at the next block.
+    int set_conv_block(size_t n);
+    size_t conv_block() const { return fc_block; }
     const void* host_taps() const { return taps.data(); }  // as given to prepare
     // Enqueue one block on `s` with the first eligible kernel; *ran_algo (sdrgpu_fir_algorithm)
     // and *kernel (sdrgpu_fir_kernel, | CU8_CONVERTED) name it.  p.sample_kind is the handle's:
@@ -58,9 +71,16 @@ private:
     void* os_state = nullptr;
     int os_status = SDRGPU_OK;
     detail::DevBuf stage_conv;  // u8 -> c64 for the kernels without fused ingest
+    void* fc_state = nullptr;   // fast convolution: plan, spectrum and twiddles of fc_block
+    int fc_status = SDRGPU_OK;
+    size_t fc_block = 0;
+    detail::DevBuf fc_slab;     // its scratch slab
+    int taps_finite = -1;       // -1: not looked at yet
 
     bool mx_shape_ok() const;
     bool os_shape_ok() const;
+    bool fc_shape_ok() const;
+    bool fc_auto_takes(const FirParams& p);
     int mx_prepare(hipStream_t s);
 };
 

@@ -29,6 +29,7 @@ FIR_AUTO = 0
 FIR_DIRECT = 1
 FIR_OVERLAP_SAVE = 2
 FIR_MATRIX = 3
+FIR_FAST_CONV = 4  # long filters: overlap-save on 2^13 .. 2^20-point blocks
 
 # sdrgpu_fir_kernel: which kernel ran the last block (last_kernel())
 FIR_KERNEL_NONE = 0
@@ -37,6 +38,7 @@ FIR_KERNEL_INT8 = 2
 FIR_KERNEL_BF16X3 = 3
 FIR_KERNEL_OVERLAP_SAVE = 4
 FIR_KERNEL_DIRECT = 5
+FIR_KERNEL_FAST_CONV = 6
 FIR_KERNEL_CU8_CONVERTED = 16
 
 FFT_OUT_COMPLEX = 0
@@ -122,6 +124,9 @@ SIGNATURES = [
     # FIR
     ("sdrgpu_fir_create", c_int, [c_int, c_int, c_int, c_void_p, c_size_t, c_uint32, _PH]),
     ("sdrgpu_fir_set_algorithm", c_int, [_H, c_int]),
+    ("sdrgpu_fir_set_conv_block", c_int, [_H, c_size_t]),
+    ("sdrgpu_fir_get_conv_block", c_int, [_H, _PS]),
+    ("sdrgpu_fir_conv_plan", c_int, [c_size_t, c_uint32, c_size_t, _PS, _PS, _PS, _PS]),
     ("sdrgpu_fir_set_stream", c_int, [_H, c_void_p]),
     ("sdrgpu_fir_get_stream", c_int, [_H, _PH]),
     ("sdrgpu_fir_output_len", c_int, [_H, c_size_t, _PS]),
@@ -138,6 +143,8 @@ SIGNATURES = [
     ("sdrgpu_firbank_create", c_int,
      [c_int, c_int, c_int, c_void_p, c_size_t, c_uint32, c_size_t, _PH]),
     ("sdrgpu_firbank_set_algorithm", c_int, [_H, c_int]),
+    ("sdrgpu_firbank_set_conv_block", c_int, [_H, c_size_t]),
+    ("sdrgpu_firbank_get_conv_block", c_int, [_H, _PS]),
     ("sdrgpu_firbank_set_stream", c_int, [_H, c_void_p]),
     ("sdrgpu_firbank_get_stream", c_int, [_H, _PH]),
     ("sdrgpu_firbank_output_len", c_int, [_H, c_size_t, _PS]),

@@ -134,6 +134,16 @@ class FirFilter:
     def set_algorithm(self, algo: int):
         check(lib().sdrgpu_fir_set_algorithm(self._h, algo), "sdrgpu_fir_set_algorithm")
 
+    def set_conv_block(self, n: int):
+        """Block size of FIR_FAST_CONV: 0 automatic, else a power of two in [2^13, 2^20] that is
+        at least 2 (ntaps - 1)."""
+        check(lib().sdrgpu_fir_set_conv_block(self._h, n), "sdrgpu_fir_set_conv_block")
+
+    def get_conv_block(self) -> int:
+        n = ctypes.c_size_t()
+        check(lib().sdrgpu_fir_get_conv_block(self._h, ctypes.byref(n)), "sdrgpu_fir_get_conv_block")
+        return n.value
+
     def set_stream(self, stream_ptr: Optional[int]):
         check(lib().sdrgpu_fir_set_stream(self._h, stream_ptr), "sdrgpu_fir_set_stream")
 
@@ -184,7 +194,7 @@ class FirFilter:
         check(lib().sdrgpu_fir_sync(self._h), "sdrgpu_fir_sync")
 
     def last_algorithm(self) -> int:
-        """FIR_DIRECT / FIR_OVERLAP_SAVE / FIR_MATRIX: the path of the last block."""
+        """FIR_DIRECT / FIR_OVERLAP_SAVE / FIR_MATRIX / FIR_FAST_CONV: the path of the last block."""
         a = ctypes.c_int()
         check(lib().sdrgpu_fir_last_algorithm(self._h, ctypes.byref(a)), "last_algorithm")
         return a.value
@@ -242,6 +252,16 @@ class FirBank:
 
     def set_algorithm(self, algo: int):
         check(lib().sdrgpu_firbank_set_algorithm(self._h, algo), "set_algorithm")
+
+    def set_conv_block(self, n: int):
+        """Block size of FIR_FAST_CONV, as FirFilter.set_conv_block."""
+        check(lib().sdrgpu_firbank_set_conv_block(self._h, n), "sdrgpu_firbank_set_conv_block")
+
+    def get_conv_block(self) -> int:
+        n = ctypes.c_size_t()
+        check(lib().sdrgpu_firbank_get_conv_block(self._h, ctypes.byref(n)),
+              "sdrgpu_firbank_get_conv_block")
+        return n.value
 
     def set_stream(self, stream_ptr: Optional[int]):
         check(lib().sdrgpu_firbank_set_stream(self._h, stream_ptr), "set_stream")
@@ -381,6 +401,15 @@ class PolyFir:
 
     def sync(self):
         check(lib().sdrgpu_polyfir_sync(self._h), "sdrgpu_polyfir_sync")
+
+
+def fir_conv_plan(ntaps: int, decim: int = 1, block: int = 0):
+    """(N, M1, M2, valid) of FIR_FAST_CONV for a filter (sdrgpu_fir_conv_plan): the block of
+    N = M1 * M2 points and the stream positions a block yields.  block = 0: the automatic N."""
+    v = [ctypes.c_size_t() for _ in range(4)]
+    check(lib().sdrgpu_fir_conv_plan(ntaps, decim, block, *[ctypes.byref(x) for x in v]),
+          "sdrgpu_fir_conv_plan")
+    return tuple(x.value for x in v)
 
 
 def polyfir_plan(up: int, down: int, consumed: int, n_in: int):
