@@ -60,8 +60,8 @@ def test_invalid_arguments_rejected_before_device(sdr):
 
 
 def test_null_handles_rejected_by_every_family(sdr):
-    """The lifecycle calls of the eight handle families that share the sdrgpu error codes: a NULL
-    handle is SDRGPU_ERR_INVALID, destroy(NULL) returns, a create without an out-pointer is
+    """The lifecycle calls of the fourteen handle families that share the sdrgpu error codes: a
+    NULL handle is SDRGPU_ERR_INVALID, destroy(NULL) returns, a create without an out-pointer is
     SDRGPU_ERR_INVALID.  (get_stream with a NULL out-pointer needs a live handle: not here.)"""
     from sdrgpu import _lib
     L = sdr.lib()
@@ -69,6 +69,8 @@ def test_null_handles_rejected_by_every_family(sdr):
     families = {  # name: has reset, has clone
         "fir": (True, True), "firbank": (True, True), "chan": (True, True), "synth": (True, True),
         "fft": (False, False), "stft": (True, False), "pll": (True, True), "biquad": (True, True),
+        "polyfir": (True, True), "tuner": (True, True), "upconv": (True, True), "demod": (True, True),
+        "agc": (True, True), "istft": (True, True),
     }
     for fam, (has_reset, has_clone) in families.items():
         fn = lambda op: getattr(L, f"sdrgpu_{fam}_{op}")
@@ -80,6 +82,9 @@ def test_null_handles_rejected_by_every_family(sdr):
         if has_clone:
             assert fn("clone")(None, ctypes.byref(out)) == _lib.ERR_INVALID, fam
         assert fn("destroy")(None) is None, fam
+        if hasattr(L, f"sdrgpu_{fam}_output_len"):
+            n = ctypes.c_size_t()
+            assert fn("output_len")(None, 16, ctypes.byref(n)) == _lib.ERR_INVALID, fam
 
     taps = np.ones(4, np.float32)
     t = taps.ctypes.data
@@ -87,6 +92,9 @@ def test_null_handles_rejected_by_every_family(sdr):
                           _lib.BiquadDesignC(_lib.BQ_IDENTITY, 0.0, 0.0),
                           _lib.BiquadDesignC(_lib.BQ_IDENTITY, 0.0, 0.0))
     bq = _lib.BiquadDesignC(_lib.BQ_LOWPASS, 1000.0, 0.707)
+    word_pair = np.zeros(2, np.uint32)
+    words = word_pair.ctypes.data
+    agc = _lib.AgcDesignC(1.0, 0.1, 0.01, 1e-6, 1e6, 1.0, 256)
     creates = {
         "fir_create": (0, _lib.C64, _lib.F32, t, 4, 1, None),
         "firbank_create": (0, _lib.C64, _lib.F32, t, 4, 1, 2, None),
@@ -99,6 +107,12 @@ def test_null_handles_rejected_by_every_family(sdr):
         "stft_create": (0, 64, 16, None),
         "pll_create": (0, ctypes.byref(pll), 1, None),
         "biquad_create": (0, _lib.F32, ctypes.byref(bq), 48000.0, 1, None),
+        "polyfir_create": (0, _lib.C64, t, 4, 3, 2, 2, None),
+        "tuner_create": (0, _lib.C64, t, 4, 2, words, 2, None),
+        "upconv_create": (0, _lib.C64, t, 4, 2, words, 2, None),
+        "demod_create": (0, _lib.C64, _lib.DEMOD_FM, 1.0, 2, None),
+        "agc_create": (0, _lib.C64, ctypes.byref(agc), 2, None),
+        "istft_create": (0, 64, 16, None, None),
     }
     for name, args in creates.items():
         assert getattr(L, "sdrgpu_" + name)(*args) == _lib.ERR_INVALID, name

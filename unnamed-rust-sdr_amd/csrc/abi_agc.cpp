@@ -6,7 +6,7 @@
 #include <cmath>
 #include <vector>
 
-#include "abi_common.hpp"
+#include "abi_bank.hpp"
 #include "agc_kernels.hpp"
 
 using namespace sdrgpu;
@@ -27,36 +27,22 @@ int check_design(const sdrgpu_agc_design* d) {
 
 }  // namespace
 
-struct sdrgpu_agc {
-    int device = 0;
+// RowBank (abi_bank.hpp): the state is nch x (g, s), one buffer that the kernels update in place;
+// stage_out2 stages the gain row, scratch holds a call's frame sums and gains
+struct sdrgpu_agc : RowBank {
     int kind = SDRGPU_C64;
     sdrgpu_agc_design design{};
     size_t nch = 1;
-    float2* d_state = nullptr;  // nch x (g, s)
-    uint32_t c = 0;             // samples counted in the open frame
+    uint32_t c = 0;  // samples counted in the open frame
     int last_form = -1, last_copied = 0;
-    StreamSlot stream;
-    DevBuf scratch, stage_in, stage_out, stage_gain, stage_alias;
 
     size_t elem() const { return kind_bytes(kind); }
-    size_t state_bytes() const { return nch * sizeof(float2); }
 
-    void free_all() {
-        DeviceGuard g_(device);
-        if (d_state) (void)hipFree(d_state);
-        d_state = nullptr;
-        for (DevBuf* b : {&scratch, &stage_in, &stage_out, &stage_gain, &stage_alias}) b->release();
-        stream.destroy();
-    }
-
-    // g = clamp(initial_gain), s = 0, c = 0 on every row, after the calls enqueued so far
+    // g = clamp(initial_gain), s = 0, c = 0 on every row
     int reset() {
-        DeviceGuard g_(device);
-        if (!g_.ok()) return SDRGPU_ERR_DEVICE;
         const float g0 = agc::clamp_gain(design.initial_gain, design.min_gain, design.max_gain);
         const std::vector<float2> st(nch, make_float2(g0, 0.0f));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        SDRGPU_HIP_TRY(hipMemcpy(d_state, st.data(), state_bytes(), hipMemcpyHostToDevice));
+        if (int e = reset_state(st.data())) return e;
         c = 0;
         return SDRGPU_OK;
     }
@@ -69,18 +55,10 @@ struct sdrgpu_agc {
         if (d->frame == 0) return SDRGPU_ERR_INVALID;
         if (sample_kind == SDRGPU_CU8 || d->frame > agc::kMaxFrame || rows > agc::kMaxCh)
             return SDRGPU_ERR_UNSUPPORTED;
-        int st = check_device(dev);
-        if (st) return st;
-        device = dev;
         kind = sample_kind;
         design = *d;
         nch = rows;
-
-        DeviceGuard g_(device);
-        if (!g_.ok()) return SDRGPU_ERR_DEVICE;
-        if ((st = stream.create())) return st;
-        SDRGPU_HIP_TRY(hipMalloc(&d_state, state_bytes()));
-        return reset();
+        return open(dev, nch * sizeof(float2), 1, [&] { return reset(); });
     }
 
     // Whether an output row set may share bytes with the input rows without a copy: it shares none,
@@ -99,11 +77,7 @@ struct sdrgpu_agc {
         if (!d_in || !d_out) return SDRGPU_ERR_INVALID;
         agc::Block plan;
         if (!agc::plan_block(design.frame, c, n, &plan)) return SDRGPU_ERR_INVALID;
-        const size_t need = plan.scratch_floats(nch) * sizeof(float);
-        if (need > scratch.cap) {  // growing frees a buffer an earlier block may still use
-            SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-            if (int st = scratch.ensure(need)) return st;
-        }
+        if (int st = grow(scratch, plan.scratch_floats(nch) * sizeof(float))) return st;
         last_copied = 0;
         if (!safe_over_input(d_in, ld_in, n, d_out, ld_out, elem()) ||
             (d_gain && !safe_over_input(d_in, ld_in, n, d_gain, ld_gain, sizeof(float)))) {
@@ -120,7 +94,7 @@ struct sdrgpu_agc {
         a.gain = d_gain;
         a.ld_gain = ld_gain;
         a.nch = nch;
-        a.state = d_state;
+        a.state = state<float2>();
         a.frame = design.frame;
         a.c = c;
         a.reference = design.reference;
@@ -140,34 +114,19 @@ struct sdrgpu_agc {
     int process_host(const void* in, size_t ld_in, size_t n, void* out, size_t ld_out, float* gain,
                      size_t ld_gain) {
         if (!in || !out) return SDRGPU_ERR_INVALID;
-        DeviceGuard g_(device);
-        if (!g_.ok()) return SDRGPU_ERR_DEVICE;
         const size_t row = n * elem(), row_g = n * sizeof(float);
-        int st;
-        if (stage_in.cap < nch * row || stage_out.cap < nch * row || (gain && stage_gain.cap < nch * row_g))
-            SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        if ((st = stage_in.ensure(nch * row))) return st;
-        if ((st = stage_out.ensure(nch * row))) return st;
-        if (gain && (st = stage_gain.ensure(nch * row_g))) return st;
-        SDRGPU_HIP_TRY(hipMemcpy2DAsync(stage_in.ptr, row, in, ld_in * elem(), row, nch, hipMemcpyHostToDevice,
-                                        stream.cur));
-        if ((st = run_dev(stage_in.ptr, n, n, stage_out.ptr, n, gain ? static_cast<float*>(stage_gain.ptr) : nullptr,
-                          n)))
-            return st;
-        SDRGPU_HIP_TRY(hipMemcpy2DAsync(out, ld_out * elem(), stage_out.ptr, row, row, nch, hipMemcpyDeviceToHost,
-                                        stream.cur));
-        if (gain)
-            SDRGPU_HIP_TRY(hipMemcpy2DAsync(gain, ld_gain * sizeof(float), stage_gain.ptr, row_g, row_g, nch,
-                                            hipMemcpyDeviceToHost, stream.cur));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        return SDRGPU_OK;
+        const HostRows gains = host_rows(gain, nch, row_g, ld_gain * sizeof(float));
+        return staged(host_rows(in, nch, row, ld_in * elem()), host_rows(out, nch, row, ld_out * elem()),
+                      gain ? &gains : nullptr, [&](void* d_in, void* d_out, void* d_gain) {
+                          return run_dev(d_in, n, n, d_out, n, static_cast<float*>(d_gain), n);
+                      });
     }
 
     int get_gains(float* g) const {
         DeviceGuard g_(device);
         if (!g_.ok()) return SDRGPU_ERR_DEVICE;
         SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        SDRGPU_HIP_TRY(hipMemcpy2D(g, sizeof(float), d_state, sizeof(float2), sizeof(float), nch,
+        SDRGPU_HIP_TRY(hipMemcpy2D(g, sizeof(float), d_state[0], sizeof(float2), sizeof(float), nch,
                                    hipMemcpyDeviceToHost));
         return SDRGPU_OK;
     }
@@ -175,11 +134,8 @@ struct sdrgpu_agc {
     int clone_into(sdrgpu_agc* dst) const {
         int st = dst->init(device, kind, &design, nch);
         if (st) return st;
-        DeviceGuard g_(device);
-        SDRGPU_HIP_TRY(hipMemcpyAsync(dst->d_state, d_state, state_bytes(), hipMemcpyDeviceToDevice, stream.cur));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
         dst->c = c;
-        return SDRGPU_OK;
+        return copy_state_to(*dst);
     }
 };
 

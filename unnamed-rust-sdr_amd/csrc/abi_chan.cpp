@@ -20,9 +20,9 @@ using namespace sdrgpu::detail;
 // c64 at 4096 channels) and every frame reads P*nch samples
 static constexpr size_t kChanMaxP = 64;
 
-// BankCore (abi_bank.hpp): d_taps is polyphase-major (chan_kernels.hpp: taps_pm), the history
+// PolyBank (abi_bank.hpp): d_taps is polyphase-major (chan_kernels.hpp: taps_pm), the history
 // P*M - 1 samples
-struct sdrgpu_chan : BankCore {
+struct sdrgpu_chan : PolyBank {
     int sk = SDRGPU_C64;
     ChanGenPlan gen;                       // general
     unsigned long long seen = 0;           // stream samples consumed
@@ -46,7 +46,12 @@ struct sdrgpu_chan : BankCore {
         // taps_pm[q*M + r] = h[q*M + M-1-r]: lane r of a wave reads consecutive floats
         std::vector<float> pm(p * nch, 0.0f);
         for (size_t n = 0; n < ntaps; ++n) pm[n / nch * nch + (nch - 1 - n % nch)] = h[n];
-        return setup(dev, h, ntaps, nch, oversample, pm, (p * nch - 1) * sizeof(float2), seen);
+        return setup(dev, h, ntaps, nch, oversample, pm, (p * nch - 1) * sizeof(float2));
+    }
+
+    int reset() {
+        seen = 0;
+        return reset_state();
     }
 
     // Enqueue one block (device pointers) on the current stream; ld_out >= out_len(n_in).
@@ -60,8 +65,8 @@ struct sdrgpu_chan : BankCore {
         ChanArgs a{};
         a.in = d_in;
         a.n_in = (long)n_in;
-        a.hist = d_hist[cur];
-        a.hist_next = d_hist[cur ^ 1];
+        a.hist = state<float2>();
+        a.hist_next = state_next<float2>();
         a.H = (long)H();
         a.pend = (long)(seen % D());
         a.os = os;
@@ -74,7 +79,7 @@ struct sdrgpu_chan : BankCore {
         a.ld_out = (long)ld_out;
         if ((st = general ? chan_gen_launch(gen, sk, a, stream.cur) : chan_launch(M, sk, a, stream.cur)))
             return st;
-        cur ^= 1;
+        flip();
         seen += n_in;
         return SDRGPU_OK;
     }
@@ -83,26 +88,16 @@ struct sdrgpu_chan : BankCore {
         const size_t n_out = out_len(n_in);
         if (n_in == 0) return SDRGPU_OK;
         if (!in || (n_out && !out)) return SDRGPU_ERR_INVALID;
-        DeviceGuard g(device);
-        if (!g.ok()) return SDRGPU_ERR_DEVICE;
-        const size_t row = n_out * sizeof(float2);
-        int st;
-        if ((st = stage_in.ensure(n_in * in_bytes()))) return st;
-        if ((st = stage_out.ensure((size_t)M * (n_out ? n_out : 1) * sizeof(float2)))) return st;
-        SDRGPU_HIP_TRY(hipMemcpyAsync(stage_in.ptr, in, n_in * in_bytes(), hipMemcpyHostToDevice, stream.cur));
-        if ((st = run_dev(stage_in.ptr, n_in, stage_out.ptr, n_out))) return st;
-        if (n_out)
-            SDRGPU_HIP_TRY(hipMemcpy2DAsync(out, ld_out * sizeof(float2), stage_out.ptr, row, row,
-                                            (size_t)M, hipMemcpyDeviceToHost, stream.cur));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        return SDRGPU_OK;
+        return staged(host_rows(in, 1, n_in * in_bytes(), 0),
+                      host_rows(out, (size_t)M, n_out * sizeof(float2), ld_out * sizeof(float2)), nullptr,
+                      [&](void* d_in, void* d_out, void*) { return run_dev(d_in, n_in, d_out, n_out); });
     }
 
     int clone_into(sdrgpu_chan* dst) const {
         int st = dst->init(device, sk, taps.data(), taps.size(), (size_t)M, (uint32_t)os, general);
         if (st) return st;
         dst->seen = seen;
-        return copy_history_to(*dst);
+        return copy_state_to(*dst);
     }
 };
 
@@ -157,18 +152,14 @@ int sdrgpu_chan_output_len(const sdrgpu_chan* h, size_t n_in, size_t* n_out) {
 int sdrgpu_chan_process(sdrgpu_chan* h, const void* in, size_t n_in, void* out, size_t ld_out,
                         size_t* n_out) {
     if (!h) return SDRGPU_ERR_INVALID;
-    const size_t need = h->out_len(n_in);
-    if (n_out) *n_out = need;
-    if (ld_out < need) return SDRGPU_ERR_OUTPUT_CAP;
+    if (int st = check_block(true, h->out_len(n_in), n_out, n_in, n_in, ld_out)) return st;
     return h->process_host(in, n_in, out, ld_out);
 }
 
 int sdrgpu_chan_process_dev(sdrgpu_chan* h, const void* d_in, size_t n_in, void* d_out,
                             size_t ld_out, size_t* n_out) {
     if (!h) return SDRGPU_ERR_INVALID;
-    const size_t need = h->out_len(n_in);
-    if (n_out) *n_out = need;
-    if (ld_out < need) return SDRGPU_ERR_OUTPUT_CAP;
+    if (int st = check_block(true, h->out_len(n_in), n_out, n_in, n_in, ld_out)) return st;
     DeviceGuard g(h->device);
     if (!g.ok()) return SDRGPU_ERR_DEVICE;
     return h->run_dev(d_in, n_in, d_out, ld_out);
@@ -176,6 +167,6 @@ int sdrgpu_chan_process_dev(sdrgpu_chan* h, const void* d_in, size_t n_in, void*
 
 int sdrgpu_chan_sync(sdrgpu_chan* h) { return h ? sync_stream(h->device, h->stream) : SDRGPU_ERR_INVALID; }
 
-int sdrgpu_chan_reset(sdrgpu_chan* h) { return h ? h->reset(h->seen) : SDRGPU_ERR_INVALID; }
+int sdrgpu_chan_reset(sdrgpu_chan* h) { return h ? h->reset() : SDRGPU_ERR_INVALID; }
 
 }  // extern "C"

@@ -6,46 +6,25 @@
 #include <cmath>
 #include <vector>
 
-#include "abi_common.hpp"
+#include "abi_bank.hpp"
 #include "demod_kernels.hpp"
 
 using namespace sdrgpu;
 using namespace sdrgpu::detail;
 
-struct sdrgpu_demod {
-    int device = 0;
+// RowBank (abi_bank.hpp): the state is the last sample of every row (c64)
+struct sdrgpu_demod : RowBank {
     int kind = SDRGPU_C64;
     int mode = SDRGPU_DEMOD_FM;
     float gain = 1.0f;
     size_t nch = 1;
-    float2* d_state[2] = {nullptr, nullptr};  // ping-pong, nch samples each
-    int cur = 0;
-    StreamSlot stream;
-    DevBuf stage_in, stage_out, stage_alias;
 
     size_t in_bytes() const { return kind_bytes(kind); }
-    size_t state_bytes() const { return nch * sizeof(float2); }
 
-    void free_all() {
-        DeviceGuard g_(device);
-        for (void* p : {(void*)d_state[0], (void*)d_state[1]})
-            if (p) (void)hipFree(p);
-        d_state[0] = d_state[1] = nullptr;
-        stage_in.release();
-        stage_out.release();
-        stage_alias.release();
-        stream.destroy();
-    }
-
-    // x[-1] = (1, 0) on every row, after the calls enqueued so far
+    // x[-1] = (1, 0) on every row
     int reset() {
-        DeviceGuard g_(device);
-        if (!g_.ok()) return SDRGPU_ERR_DEVICE;
         const std::vector<float2> one(nch, make_float2(1.0f, 0.0f));
-        cur = 0;
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        SDRGPU_HIP_TRY(hipMemcpy(d_state[0], one.data(), state_bytes(), hipMemcpyHostToDevice));
-        return SDRGPU_OK;
+        return reset_state(one.data());
     }
 
     int init(int dev, int sample_kind, int m, float g, size_t rows) {
@@ -56,20 +35,11 @@ struct sdrgpu_demod {
             m != SDRGPU_DEMOD_POWER)
             return SDRGPU_ERR_INVALID;
         if (sample_kind == SDRGPU_F32 || rows > demod::kMaxCh) return SDRGPU_ERR_UNSUPPORTED;
-        int st = check_device(dev);
-        if (st) return st;
-        device = dev;
         kind = sample_kind;
         mode = m;
         gain = g;
         nch = rows;
-
-        DeviceGuard g_(device);
-        if (!g_.ok()) return SDRGPU_ERR_DEVICE;
-        if ((st = stream.create())) return st;
-        SDRGPU_HIP_TRY(hipMalloc(&d_state[0], state_bytes()));
-        SDRGPU_HIP_TRY(hipMalloc(&d_state[1], state_bytes()));
-        return reset();
+        return open(dev, nch * sizeof(float2), 2, [&] { return reset(); });
     }
 
     // Enqueue one block (device pointers) on the current stream, n > 0.
@@ -89,38 +59,23 @@ struct sdrgpu_demod {
         a.out = d_out;
         a.ld_out = ld_out;
         a.nch = nch;
-        a.state = d_state[cur];
-        a.state_next = d_state[cur ^ 1];
+        a.state = state<float2>();
+        a.state_next = state_next<float2>();
         if (int st = demod_launch(a, stream.cur)) return st;
-        cur ^= 1;
+        flip();
         return SDRGPU_OK;
     }
 
     int process_host(const void* in, size_t ld_in, size_t n, float* out, size_t ld_out) {
         if (!in || !out) return SDRGPU_ERR_INVALID;
-        DeviceGuard g_(device);
-        if (!g_.ok()) return SDRGPU_ERR_DEVICE;
-        const size_t row_in = n * in_bytes(), row_out = n * sizeof(float);
-        int st;
-        if ((st = stage_in.ensure(nch * row_in))) return st;
-        if ((st = stage_out.ensure(nch * row_out))) return st;
-        SDRGPU_HIP_TRY(hipMemcpy2DAsync(stage_in.ptr, row_in, in, ld_in * in_bytes(), row_in, nch,
-                                        hipMemcpyHostToDevice, stream.cur));
-        if ((st = run_dev(stage_in.ptr, n, n, static_cast<float*>(stage_out.ptr), n))) return st;
-        SDRGPU_HIP_TRY(hipMemcpy2DAsync(out, ld_out * sizeof(float), stage_out.ptr, row_out, row_out, nch,
-                                        hipMemcpyDeviceToHost, stream.cur));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        return SDRGPU_OK;
+        return staged(host_rows(in, nch, n * in_bytes(), ld_in * in_bytes()),
+                      host_rows(out, nch, n * sizeof(float), ld_out * sizeof(float)), nullptr,
+                      [&](void* d_in, void* d_out, void*) { return run_dev(d_in, n, n, static_cast<float*>(d_out), n); });
     }
 
     int clone_into(sdrgpu_demod* dst) const {
         int st = dst->init(device, kind, mode, gain, nch);
-        if (st) return st;
-        DeviceGuard g_(device);
-        SDRGPU_HIP_TRY(hipMemcpyAsync(dst->d_state[0], d_state[cur], state_bytes(), hipMemcpyDeviceToDevice,
-                                      stream.cur));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        return SDRGPU_OK;
+        return st ? st : copy_state_to(*dst);
     }
 };
 

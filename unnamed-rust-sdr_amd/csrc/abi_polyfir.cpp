@@ -6,14 +6,14 @@
 // handful of integers of polyfir_plan.hpp, nothing per frame.
 #include <vector>
 
-#include "abi_common.hpp"
+#include "abi_bank.hpp"
 #include "polyfir_kernels.hpp"
 
 using namespace sdrgpu;
 using namespace sdrgpu::detail;
 
-struct sdrgpu_polyfir {
-    int device = 0;
+// RowBank (abi_bank.hpp): the state is the last g.T - 1 inputs of every row, of the handle's kind
+struct sdrgpu_polyfir : RowBank {
     int kind = SDRGPU_C64;
     size_t nch = 1;
     std::vector<float> taps;  // as given (clone)
@@ -22,36 +22,13 @@ struct sdrgpu_polyfir {
     float* d_taps = nullptr;
     float* d_image = nullptr;  // staged form
     int2* d_tab = nullptr;
-    void* d_hist[2] = {nullptr, nullptr};  // ping-pong, hist_bytes each
-    size_t hist_bytes = 0;
-    int cur = 0;
     unsigned long long consumed = 0;  // inputs per row so far
-    StreamSlot stream;
-    DevBuf stage_in, stage_out, stage_alias;
 
     size_t elem() const { return kind_bytes(kind); }
 
-    void free_all() {
-        DeviceGuard g_(device);
-        for (void* p : {(void*)d_taps, (void*)d_image, (void*)d_tab, d_hist[0], d_hist[1]})
-            if (p) (void)hipFree(p);
-        d_taps = d_image = nullptr;
-        d_tab = nullptr;
-        d_hist[0] = d_hist[1] = nullptr;
-        stage_in.release();
-        stage_out.release();
-        stage_alias.release();
-        stream.destroy();
-    }
-
     int reset() {
-        DeviceGuard g_(device);
-        if (!g_.ok()) return SDRGPU_ERR_DEVICE;
         consumed = 0;
-        cur = 0;
-        SDRGPU_HIP_TRY(hipMemsetAsync(d_hist[0], 0, hist_bytes, stream.cur));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        return SDRGPU_OK;
+        return reset_state();
     }
 
     int init(int dev, int sample_kind, const float* h, size_t ntaps, uint32_t up, uint32_t down, size_t rows) {
@@ -61,34 +38,24 @@ struct sdrgpu_polyfir {
         if (sample_kind == SDRGPU_CU8 || up > polyfir::kMaxRatio || down > polyfir::kMaxRatio ||
             (ntaps + up - 1) / up > polyfir::kMaxReach || rows > polyfir::kMaxRows)
             return SDRGPU_ERR_UNSUPPORTED;
-        int st = check_device(dev);
-        if (st) return st;
-        device = dev;
         kind = sample_kind;
         nch = rows;
         taps.assign(h, h + ntaps);
         g = polyfir::geometry(up, down, ntaps);
         form = polyfir_form(g);
         const size_t hl = g.T - 1;
-        hist_bytes = (hl ? hl * nch : 1) * elem();
-
-        DeviceGuard g_(device);
-        if (!g_.ok()) return SDRGPU_ERR_DEVICE;
-        if ((st = stream.create())) return st;
-        SDRGPU_HIP_TRY(hipMalloc(&d_taps, ntaps * sizeof(float)));
-        SDRGPU_HIP_TRY(hipMemcpy(d_taps, h, ntaps * sizeof(float), hipMemcpyHostToDevice));
-        if (form.staged) {
-            std::vector<float> image;
-            std::vector<int2> tab;
-            polyfir_tables(g, form, h, ntaps, image, tab);
-            SDRGPU_HIP_TRY(hipMalloc(&d_image, image.size() * sizeof(float)));
-            SDRGPU_HIP_TRY(hipMemcpy(d_image, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice));
-            SDRGPU_HIP_TRY(hipMalloc(&d_tab, tab.size() * sizeof(int2)));
-            SDRGPU_HIP_TRY(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice));
-        }
-        SDRGPU_HIP_TRY(hipMalloc(&d_hist[0], hist_bytes));
-        SDRGPU_HIP_TRY(hipMalloc(&d_hist[1], hist_bytes));
-        return reset();
+        return open(dev, (hl ? hl * nch : 1) * elem(), 2, [&] {
+            int st;
+            if ((st = upload(&d_taps, h, ntaps))) return st;
+            if (form.staged) {
+                std::vector<float> image;
+                std::vector<int2> tab;
+                polyfir_tables(g, form, h, ntaps, image, tab);
+                if ((st = upload(&d_image, image.data(), image.size()))) return st;
+                if ((st = upload(&d_tab, tab.data(), tab.size()))) return st;
+            }
+            return reset();
+        });
     }
 
     // Enqueue one block (device pointers) on the current stream: b is the call's plan, n > 0.
@@ -104,8 +71,8 @@ struct sdrgpu_polyfir {
         a.in = d_in;
         a.ld_in = (long)ld_in;
         a.n_in = (long)n;
-        a.hist = d_hist[cur];
-        a.hist_next = d_hist[cur ^ 1];
+        a.hist = state();
+        a.hist_next = state_next();
         a.out = d_out;
         a.ld_out = (long)ld_out;
         a.n_out = (long)b.n_out;
@@ -118,38 +85,23 @@ struct sdrgpu_polyfir {
         a.g = g;
         a.o = polyfir::origin(g, consumed, b.first_out);
         if (int st = polyfir_launch(form, a, stream.cur)) return st;
-        if (g.T > 1) cur ^= 1;
+        if (g.T > 1) flip();
         consumed += n;
         return SDRGPU_OK;
     }
 
     int process_host(const void* in, size_t ld_in, size_t n, void* out, size_t ld_out, const polyfir::Block& b) {
         if (!in || (b.n_out && !out)) return SDRGPU_ERR_INVALID;
-        DeviceGuard g_(device);
-        if (!g_.ok()) return SDRGPU_ERR_DEVICE;
-        const size_t e = elem(), row_in = n * e, row_out = b.n_out * e;
-        int st;
-        if ((st = stage_in.ensure(nch * row_in))) return st;
-        if ((st = stage_out.ensure(nch * row_out))) return st;
-        SDRGPU_HIP_TRY(hipMemcpy2DAsync(stage_in.ptr, row_in, in, ld_in * e, row_in, nch,
-                                        hipMemcpyHostToDevice, stream.cur));
-        if ((st = run_dev(stage_in.ptr, n, n, stage_out.ptr, b.n_out, b))) return st;
-        if (b.n_out)
-            SDRGPU_HIP_TRY(hipMemcpy2DAsync(out, ld_out * e, stage_out.ptr, row_out, row_out, nch,
-                                            hipMemcpyDeviceToHost, stream.cur));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        return SDRGPU_OK;
+        const size_t e = elem();
+        return staged(host_rows(in, nch, n * e, ld_in * e), host_rows(out, nch, b.n_out * e, ld_out * e), nullptr,
+                      [&](void* d_in, void* d_out, void*) { return run_dev(d_in, n, n, d_out, b.n_out, b); });
     }
 
     int clone_into(sdrgpu_polyfir* dst) const {
         int st = dst->init(device, kind, taps.data(), taps.size(), g.L, g.D, nch);
         if (st) return st;
         dst->consumed = consumed;
-        DeviceGuard g_(device);
-        SDRGPU_HIP_TRY(hipMemcpyAsync(dst->d_hist[0], d_hist[cur], hist_bytes, hipMemcpyDeviceToDevice,
-                                      stream.cur));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        return SDRGPU_OK;
+        return copy_state_to(*dst);
     }
 };
 
@@ -159,12 +111,8 @@ namespace {
 int check_block(const sdrgpu_polyfir* h, size_t ld_in, size_t n_in, size_t ld_out, size_t* n_out,
                 polyfir::Block* b) {
     if (!h) return SDRGPU_ERR_INVALID;
-    if (!polyfir::plan_block(h->g.L, h->g.D, h->consumed, n_in, b)) return SDRGPU_ERR_INVALID;
-    if (n_out) *n_out = (size_t)b->n_out;
-    if (n_in == 0) return SDRGPU_OK;
-    if (ld_in < n_in) return SDRGPU_ERR_INVALID;
-    if (b->n_out > ld_out) return SDRGPU_ERR_OUTPUT_CAP;
-    return SDRGPU_OK;
+    const bool ok = polyfir::plan_block(h->g.L, h->g.D, h->consumed, n_in, b);
+    return detail::check_block(ok, ok ? (size_t)b->n_out : 0, n_out, n_in, ld_in, ld_out);
 }
 
 }  // namespace

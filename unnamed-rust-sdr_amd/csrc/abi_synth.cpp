@@ -17,9 +17,9 @@ using namespace sdrgpu::detail;
 // frames that reach one output sample at most, as ceil(ntaps / D): the history is M*(Q - 1) frames
 static constexpr size_t kSynthMaxReach = 64;
 
-// BankCore (abi_bank.hpp): d_taps is the prototype, zero past the last tap, the history the last
+// PolyBank (abi_bank.hpp): d_taps is the prototype, zero past the last tap, the history the last
 // Q - 1 frames of every row
-struct sdrgpu_synth : BankCore {
+struct sdrgpu_synth : PolyBank {
     SynthGenPlan gen;                        // general
     unsigned long long frames = 0;           // frames consumed per channel
 
@@ -37,7 +37,12 @@ struct sdrgpu_synth : BankCore {
         std::vector<float> padded(p * nch, 0.0f);
         std::copy(g, g + ntaps, padded.begin());
         const size_t hist_len = nch * (p * oversample - 1);
-        return setup(dev, g, ntaps, nch, oversample, padded, (hist_len ? hist_len : 1) * sizeof(float2), frames);
+        return setup(dev, g, ntaps, nch, oversample, padded, (hist_len ? hist_len : 1) * sizeof(float2));
+    }
+
+    int reset() {
+        frames = 0;
+        return reset_state();
     }
 
     // Enqueue one block (device pointers) on the current stream; ld_in >= n, d_out holds n*D.
@@ -61,8 +66,8 @@ struct sdrgpu_synth : BankCore {
         a.in = static_cast<const float2*>(d_in);
         a.ld_in = (long)ld_in;
         a.nframes = (long)n;
-        a.hist = d_hist[cur];
-        a.hist_next = d_hist[cur ^ 1];
+        a.hist = state<float2>();
+        a.hist_next = state_next<float2>();
         a.Q = (int)Q();
         a.HQ = (long)Q() - 1;
         a.os = os;
@@ -74,7 +79,7 @@ struct sdrgpu_synth : BankCore {
         a.n_out = (long)n_out;
         if (int st = general ? synth_gen_launch(gen, a, stream.cur) : synth_launch(M, a, stream.cur))
             return st;
-        cur ^= 1;
+        flip();
         frames += n;
         return SDRGPU_OK;
     }
@@ -82,26 +87,16 @@ struct sdrgpu_synth : BankCore {
     int process_host(const void* in, size_t ld_in, size_t n, void* out) {
         if (n == 0) return SDRGPU_OK;
         if (!in || !out) return SDRGPU_ERR_INVALID;
-        DeviceGuard g(device);
-        if (!g.ok()) return SDRGPU_ERR_DEVICE;
-        const size_t row = n * sizeof(float2), n_out = n * D();
-        int st;
-        if ((st = stage_in.ensure((size_t)M * row))) return st;
-        if ((st = stage_out.ensure(n_out * sizeof(float2)))) return st;
-        SDRGPU_HIP_TRY(hipMemcpy2DAsync(stage_in.ptr, row, in, ld_in * sizeof(float2), row, (size_t)M,
-                                        hipMemcpyHostToDevice, stream.cur));
-        if ((st = run_dev(stage_in.ptr, n, n, stage_out.ptr))) return st;
-        SDRGPU_HIP_TRY(hipMemcpyAsync(out, stage_out.ptr, n_out * sizeof(float2), hipMemcpyDeviceToHost,
-                                      stream.cur));
-        SDRGPU_HIP_TRY(hipStreamSynchronize(stream.cur));
-        return SDRGPU_OK;
+        const size_t row = n * sizeof(float2);
+        return staged(host_rows(in, (size_t)M, row, ld_in * sizeof(float2)), host_rows(out, 1, row * D(), 0), nullptr,
+                      [&](void* d_in, void* d_out, void*) { return run_dev(d_in, n, n, d_out); });
     }
 
     int clone_into(sdrgpu_synth* dst) const {
         int st = dst->init(device, taps.data(), taps.size(), (size_t)M, (uint32_t)os, general);
         if (st) return st;
         dst->frames = frames;
-        return copy_history_to(*dst);
+        return copy_state_to(*dst);
     }
 };
 
@@ -110,12 +105,7 @@ namespace {
 // what both process calls check before anything is enqueued
 int check_block(const sdrgpu_synth* h, size_t ld_in, size_t n_frames, size_t out_cap, size_t* n_out) {
     if (!h) return SDRGPU_ERR_INVALID;
-    const size_t need = n_frames * h->D();
-    if (n_out) *n_out = need;
-    if (n_frames == 0) return SDRGPU_OK;
-    if (ld_in < n_frames) return SDRGPU_ERR_INVALID;
-    if (out_cap < need) return SDRGPU_ERR_OUTPUT_CAP;
-    return SDRGPU_OK;
+    return detail::check_block(true, n_frames * h->D(), n_out, n_frames, ld_in, out_cap);
 }
 
 }  // namespace
@@ -177,6 +167,6 @@ int sdrgpu_synth_process_dev(sdrgpu_synth* h, const void* d_in, size_t ld_in, si
 
 int sdrgpu_synth_sync(sdrgpu_synth* h) { return h ? sync_stream(h->device, h->stream) : SDRGPU_ERR_INVALID; }
 
-int sdrgpu_synth_reset(sdrgpu_synth* h) { return h ? h->reset(h->frames) : SDRGPU_ERR_INVALID; }
+int sdrgpu_synth_reset(sdrgpu_synth* h) { return h ? h->reset() : SDRGPU_ERR_INVALID; }
 
 }  // extern "C"

@@ -14,11 +14,11 @@ The way back has no reference counterpart (include/sdrgpu.h defines it): `FftPla
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
 
 import numpy as np
 
 from . import _lib
+from ._handle import Handle, HasOutputLen, Resets
 from ._lib import check, lib
 
 
@@ -34,39 +34,21 @@ def _out_mode(output: str) -> int:
     return _lib.FFT_OUT_DB if output == "db" else _lib.FFT_OUT_COMPLEX
 
 
-class FftPlan:
+class FftPlan(Handle):
     """A planned N-point forward FFT with fft.rs collation (plan once, unlike fft.rs:10-11).
 
     output='db' returns f32 20*log10(|value|) per bin instead of the complex value -- the
     spectrum plots' conversion (src/plot/complexseries.rs:90-92) fused into the store."""
 
+    _family = "fft"
+
     def __init__(self, n: int, device: int = 0, output: str = "complex"):
         self.n = int(n)
         self.device = device
         self.output = output
-        self._h = ctypes.c_void_p()
-        check(lib().sdrgpu_fft_plan(device, self.n, ctypes.byref(self._h)), "sdrgpu_fft_plan")
-        check(lib().sdrgpu_fft_set_output(self._h, _out_mode(output)), "sdrgpu_fft_set_output")
+        self._open("plan", device, self.n)
+        self._call("set_output", _out_mode(output))
         self._odt = np.float32 if output == "db" else np.complex64
-
-    def close(self):
-        if self._h:
-            lib().sdrgpu_fft_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_ptr: Optional[int]):
-        check(lib().sdrgpu_fft_set_stream(self._h, stream_ptr), "sdrgpu_fft_set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_fft_get_stream(self._h, ctypes.byref(s)), "get_stream")
-        return s.value or 0
 
     def exec(self, x) -> np.ndarray:
         """x: (count, n) or (n,) complex -> collated spectra of the same shape."""
@@ -95,9 +77,6 @@ class FftPlan:
     def exec_real_dev(self, d_in: int, d_out: int, count: int):
         """rfft of `count` device-resident frames (n f32 each) -> n - n/2 outputs per frame."""
         check(lib().sdrgpu_rfft_exec_dev(self._h, d_in, d_out, count), "sdrgpu_rfft_exec_dev")
-
-    def sync(self):
-        check(lib().sdrgpu_fft_sync(self._h), "sdrgpu_fft_sync")
 
     def inverse(self, x) -> np.ndarray:
         """x: (count, n) or (n,) collated spectra (what exec returns) -> the frames' samples, same
@@ -146,22 +125,22 @@ def istft_window(n: int, hop: int, analysis=None) -> np.ndarray:
     return out
 
 
-class Stft:
+class Stft(Resets, HasOutputLen, Handle):
     """Streaming Window(n) + Decimate(hop) + fft (adapters/mod.rs:270-303, 13-41).
 
     input_kind=CU8 takes raw rtl_tcp I/Q bytes (examples/live.rs windows rtl.listen()
     directly); output='db' yields f32 dB magnitudes (src/plot/complexseries.rs:90-92)."""
+
+    _family = "stft"
 
     def __init__(self, n: int, hop: int, device: int = 0, input_kind: int = _lib.C64,
                  output: str = "complex"):
         self.n, self.hop, self.device = int(n), int(hop), device
         self.input_kind, self.output = input_kind, output
         self._odt = np.float32 if output == "db" else np.complex64
-        self._h = ctypes.c_void_p()
-        check(lib().sdrgpu_stft_create(device, self.n, self.hop, ctypes.byref(self._h)),
-              "sdrgpu_stft_create")
-        check(lib().sdrgpu_stft_set_input_kind(self._h, input_kind), "sdrgpu_stft_set_input_kind")
-        check(lib().sdrgpu_stft_set_output(self._h, _out_mode(output)), "sdrgpu_stft_set_output")
+        self._open("create", device, self.n, self.hop)
+        self._call("set_input_kind", input_kind)
+        self._call("set_output", _out_mode(output))
 
     def _as_in(self, x):
         if self.input_kind == _lib.CU8:
@@ -170,30 +149,6 @@ class Stft:
 
     def _nsamp(self, x):
         return x.size // 2 if self.input_kind == _lib.CU8 else x.size
-
-    def close(self):
-        if self._h:
-            lib().sdrgpu_stft_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_ptr: Optional[int]):
-        check(lib().sdrgpu_stft_set_stream(self._h, stream_ptr), "sdrgpu_stft_set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_stft_get_stream(self._h, ctypes.byref(s)), "get_stream")
-        return s.value or 0
-
-    def output_len(self, n_in: int) -> int:
-        n = ctypes.c_size_t()
-        check(lib().sdrgpu_stft_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
-        return n.value
 
     def process(self, x) -> np.ndarray:
         x = self._as_in(x)
@@ -219,22 +174,18 @@ class Stft:
                                             ctypes.byref(got)), "sdrgpu_stft_process_dev")
         return got.value
 
-    def reset(self):
-        check(lib().sdrgpu_stft_reset(self._h), "sdrgpu_stft_reset")
-
-    def sync(self):
-        check(lib().sdrgpu_stft_sync(self._h), "sdrgpu_stft_sync")
-
     def inverse(self, window="cola") -> "Istft":
         """The matching Istft (same n, hop, device): with window='cola' its output for this handle's
         complex frames is the input stream delayed by n - hop."""
         return Istft(self.n, self.hop, window, self.device)
 
 
-class Istft:
+class Istft(Resets, Handle):
     """Streaming inverse of Stft: collated spectrum frames (n values each) back into one stream by
     windowed overlap-add, hop samples out per frame; sample u of the output is stream sample
     u - (n - hop) of the Stft's input.  window: 'cola' (istft_window(n, hop)), None (ones) or n reals."""
+
+    _family = "istft"
 
     def __init__(self, n: int, hop: int, window="cola", device: int = 0, _handle=None):
         self.n, self.hop, self.device = int(n), int(hop), device
@@ -245,51 +196,23 @@ class Istft:
         self.window = None if window is None else np.ascontiguousarray(window, np.float32)
         if self.window is not None and self.window.shape != (self.n,):
             raise _lib.SdrGpuError(_lib.ERR_INVALID, "window must have n entries")
-        self._h = ctypes.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-            return
         w = None if self.window is None else self.window.ctypes.data
-        check(lib().sdrgpu_istft_create(device, self.n, self.hop, w, ctypes.byref(self._h)),
-              "sdrgpu_istft_create")
-
-    def close(self):
-        if self._h:
-            lib().sdrgpu_istft_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_ptr: Optional[int]):
-        check(lib().sdrgpu_istft_set_stream(self._h, stream_ptr), "sdrgpu_istft_set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_istft_get_stream(self._h, ctypes.byref(s)), "get_stream")
-        return s.value or 0
+        self._open("create", device, self.n, self.hop, w, _handle=_handle)
 
     def set_batch(self, frames: int):
         """Frames per internal batch (0: automatic); only before the first frame or after reset.
         Changes no output bit (tests cut batches small with it)."""
-        check(lib().sdrgpu_istft_set_batch(self._h, int(frames)), "sdrgpu_istft_set_batch")
+        self._call("set_batch", int(frames))
 
     def set_route(self, route: int):
         """_lib.ISTFT_AUTO / ISTFT_GENERAL / ISTFT_TILE; only before the first frame or after reset."""
-        check(lib().sdrgpu_istft_set_route(self._h, int(route)), "sdrgpu_istft_set_route")
+        self._call("set_route", int(route))
 
     def route(self) -> int:
-        r = ctypes.c_int()
-        check(lib().sdrgpu_istft_get_route(self._h, ctypes.byref(r)), "sdrgpu_istft_get_route")
-        return r.value
+        return self._get(ctypes.c_int, "get_route")
 
     def output_len(self, n_frames: int) -> int:
-        n = ctypes.c_size_t()
-        check(lib().sdrgpu_istft_output_len(self._h, n_frames, ctypes.byref(n)), "output_len")
-        return n.value
+        return self._get(ctypes.c_size_t, "output_len", n_frames)
 
     def process(self, frames) -> np.ndarray:
         """frames: (count, n) or (n,) collated spectra -> count * hop samples."""
@@ -307,13 +230,7 @@ class Istft:
                                              ctypes.byref(got)), "sdrgpu_istft_process_dev")
         return got.value
 
-    def reset(self):
-        check(lib().sdrgpu_istft_reset(self._h), "sdrgpu_istft_reset")
-
     def clone(self) -> "Istft":
-        h = ctypes.c_void_p()
-        check(lib().sdrgpu_istft_clone(self._h, ctypes.byref(h)), "sdrgpu_istft_clone")
+        h = self._clone_handle()
         return Istft(self.n, self.hop, self.window, self.device, _handle=h)
 
-    def sync(self):
-        check(lib().sdrgpu_istft_sync(self._h), "sdrgpu_istft_sync")

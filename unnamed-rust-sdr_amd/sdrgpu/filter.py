@@ -24,6 +24,7 @@ from typing import Optional, Sequence, Union
 import numpy as np
 
 from . import _lib
+from ._handle import Handle, HasOutputLen, Resets, TuningWords
 from ._lib import C64, CU8, F32, check, lib
 
 
@@ -91,8 +92,10 @@ class Fir:
         return self.design(signal.rate(), getattr(signal, "sample_kind", None))
 
 
-class FirFilter:
+class FirFilter(Resets, HasOutputLen, Handle):
     """GPU Fir<C, A> handle (fir.rs:6-32) with optional fused decimation."""
+
+    _family = "fir"
 
     def __init__(self, coef: np.ndarray, sample_kind: int, decim: int = 1, device: int = 0,
                  algorithm: int = _lib.FIR_AUTO, _handle=None):
@@ -101,61 +104,25 @@ class FirFilter:
         self.coef = coef
         self.decim = decim
         self.device = device
-        self._h = ctypes.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            check(lib().sdrgpu_fir_create(device, sample_kind, self.tap_kind,
-                                          coef.ctypes.data, coef.size, decim,
-                                          ctypes.byref(self._h)), "sdrgpu_fir_create")
+        self._open("create", device, sample_kind, self.tap_kind, coef.ctypes.data, coef.size, decim,
+                   _handle=_handle)
         if algorithm != _lib.FIR_AUTO:
             self.set_algorithm(algorithm)
 
-    # -- handle management (SampleRate-style, resample.rs:32-110) --
-    def close(self):
-        if self._h:
-            lib().sdrgpu_fir_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def clone(self) -> "FirFilter":
-        h = ctypes.c_void_p()
-        check(lib().sdrgpu_fir_clone(self._h, ctypes.byref(h)), "sdrgpu_fir_clone")
+        h = self._clone_handle()
         return FirFilter(self.coef, self.sample_kind, self.decim, self.device, _handle=h)
 
-    def reset(self):
-        check(lib().sdrgpu_fir_reset(self._h), "sdrgpu_fir_reset")
-
     def set_algorithm(self, algo: int):
-        check(lib().sdrgpu_fir_set_algorithm(self._h, algo), "sdrgpu_fir_set_algorithm")
+        self._call("set_algorithm", algo)
 
     def set_conv_block(self, n: int):
         """Block size of FIR_FAST_CONV: 0 automatic, else a power of two in [2^13, 2^20] that is
         at least 2 (ntaps - 1)."""
-        check(lib().sdrgpu_fir_set_conv_block(self._h, n), "sdrgpu_fir_set_conv_block")
+        self._call("set_conv_block", n)
 
     def get_conv_block(self) -> int:
-        n = ctypes.c_size_t()
-        check(lib().sdrgpu_fir_get_conv_block(self._h, ctypes.byref(n)), "sdrgpu_fir_get_conv_block")
-        return n.value
-
-    def set_stream(self, stream_ptr: Optional[int]):
-        check(lib().sdrgpu_fir_set_stream(self._h, stream_ptr), "sdrgpu_fir_set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_fir_get_stream(self._h, ctypes.byref(s)), "sdrgpu_fir_get_stream")
-        return s.value or 0
-
-    def output_len(self, n_in: int) -> int:
-        n = ctypes.c_size_t()
-        check(lib().sdrgpu_fir_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
-        return n.value
+        return self._get(ctypes.c_size_t, "get_conv_block")
 
     # -- processing --
     def process(self, x) -> np.ndarray:
@@ -190,25 +157,20 @@ class FirFilter:
                                            ctypes.byref(got)), "sdrgpu_fir_process_dev")
         return got.value
 
-    def sync(self):
-        check(lib().sdrgpu_fir_sync(self._h), "sdrgpu_fir_sync")
-
     def last_algorithm(self) -> int:
         """FIR_DIRECT / FIR_OVERLAP_SAVE / FIR_MATRIX / FIR_FAST_CONV: the path of the last block."""
-        a = ctypes.c_int()
-        check(lib().sdrgpu_fir_last_algorithm(self._h, ctypes.byref(a)), "last_algorithm")
-        return a.value
+        return self._get(ctypes.c_int, "last_algorithm")
 
     def last_kernel(self) -> int:
         """FIR_KERNEL_*: the kernel of the last block (| FIR_KERNEL_CU8_CONVERTED when u8
         input was converted to c64 by its own launch first)."""
-        a = ctypes.c_int()
-        check(lib().sdrgpu_fir_last_kernel(self._h, ctypes.byref(a)), "last_kernel")
-        return a.value
+        return self._get(ctypes.c_int, "last_kernel")
 
 
-class FirBank:
+class FirBank(Resets, HasOutputLen, Handle):
     """nch independent Fir<C,A> (fir.rs:6-32) sharing taps; channel-major blocks."""
+
+    _family = "firbank"
 
     def __init__(self, coef, nch: int, sample_kind: int = C64, decim: int = 1,
                  device: int = 0, algorithm: int = _lib.FIR_AUTO, _handle=None):
@@ -219,62 +181,25 @@ class FirBank:
         self.sample_kind = sample_kind
         self.decim = decim
         self.device = device
-        self._h = ctypes.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            check(lib().sdrgpu_firbank_create(device, sample_kind, self.tap_kind,
-                                              self.coef.ctypes.data, self.coef.size, decim,
-                                              nch, ctypes.byref(self._h)),
-                  "sdrgpu_firbank_create")
+        self._open("create", device, sample_kind, self.tap_kind, self.coef.ctypes.data, self.coef.size,
+                   decim, nch, _handle=_handle)
         if algorithm != _lib.FIR_AUTO:
             self.set_algorithm(algorithm)
 
-    def close(self):
-        if self._h:
-            lib().sdrgpu_firbank_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def clone(self) -> "FirBank":
-        h = ctypes.c_void_p()
-        check(lib().sdrgpu_firbank_clone(self._h, ctypes.byref(h)), "sdrgpu_firbank_clone")
+        h = self._clone_handle()
         return FirBank(self.coef, self.nch, self.sample_kind, self.decim, self.device,
                        _handle=h)
 
-    def reset(self):
-        check(lib().sdrgpu_firbank_reset(self._h), "sdrgpu_firbank_reset")
-
     def set_algorithm(self, algo: int):
-        check(lib().sdrgpu_firbank_set_algorithm(self._h, algo), "set_algorithm")
+        self._call("set_algorithm", algo)
 
     def set_conv_block(self, n: int):
         """Block size of FIR_FAST_CONV, as FirFilter.set_conv_block."""
-        check(lib().sdrgpu_firbank_set_conv_block(self._h, n), "sdrgpu_firbank_set_conv_block")
+        self._call("set_conv_block", n)
 
     def get_conv_block(self) -> int:
-        n = ctypes.c_size_t()
-        check(lib().sdrgpu_firbank_get_conv_block(self._h, ctypes.byref(n)),
-              "sdrgpu_firbank_get_conv_block")
-        return n.value
-
-    def set_stream(self, stream_ptr: Optional[int]):
-        check(lib().sdrgpu_firbank_set_stream(self._h, stream_ptr), "set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_firbank_get_stream(self._h, ctypes.byref(s)), "get_stream")
-        return s.value or 0
-
-    def output_len(self, n_in: int) -> int:
-        n = ctypes.c_size_t()
-        check(lib().sdrgpu_firbank_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
-        return n.value
+        return self._get(ctypes.c_size_t, "get_conv_block")
 
     def process(self, x) -> np.ndarray:
         """x: (nch, n) host array -> (nch, n_out)."""
@@ -300,26 +225,21 @@ class FirBank:
               "sdrgpu_firbank_process_dev")
         return got.value
 
-    def sync(self):
-        check(lib().sdrgpu_firbank_sync(self._h), "sdrgpu_firbank_sync")
-
     def last_algorithm(self) -> int:
-        a = ctypes.c_int()
-        check(lib().sdrgpu_firbank_last_algorithm(self._h, ctypes.byref(a)), "last_algorithm")
-        return a.value
+        return self._get(ctypes.c_int, "last_algorithm")
 
     def last_kernel(self) -> int:
-        a = ctypes.c_int()
-        check(lib().sdrgpu_firbank_last_kernel(self._h, ctypes.byref(a)), "last_kernel")
-        return a.value
+        return self._get(ctypes.c_int, "last_kernel")
 
 
 # -------------------------------------------------------------------------- PolyFir
-class PolyFir:
+class PolyFir(Resets, HasOutputLen, Handle):
     """Rational-rate polyphase FIR ("upfirdn", sdrgpu_polyfir): per row, zero-stuff by `up`,
     signal.filter(taps) (fir.rs:23-32), .decimate by `down` (adapters/mod.rs:30-37), with only the
     kept outputs and the non-zero products computed.  floor(n*up/down) outputs exist after n
     inputs; no gain is applied (scale the taps by `up`).  State carries across blocks."""
+
+    _family = "polyfir"
 
     def __init__(self, taps, up: int, down: int, nch: int = 1, sample_kind: int = C64,
                  device: int = 0, _handle=None):
@@ -331,47 +251,13 @@ class PolyFir:
         self.nch = int(nch)
         self.sample_kind = sample_kind
         self.device = device
-        self._h = ctypes.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            check(lib().sdrgpu_polyfir_create(device, sample_kind, self.taps.ctypes.data,
-                                              self.taps.size, self.up, self.down, self.nch,
-                                              ctypes.byref(self._h)), "sdrgpu_polyfir_create")
-
-    def close(self):
-        if self._h:
-            lib().sdrgpu_polyfir_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open("create", device, sample_kind, self.taps.ctypes.data, self.taps.size, self.up,
+                   self.down, self.nch, _handle=_handle)
 
     def clone(self) -> "PolyFir":
-        h = ctypes.c_void_p()
-        check(lib().sdrgpu_polyfir_clone(self._h, ctypes.byref(h)), "sdrgpu_polyfir_clone")
+        h = self._clone_handle()
         return PolyFir(self.taps, self.up, self.down, self.nch, self.sample_kind, self.device,
                        _handle=h)
-
-    def reset(self):
-        check(lib().sdrgpu_polyfir_reset(self._h), "sdrgpu_polyfir_reset")
-
-    def set_stream(self, stream_ptr: Optional[int]):
-        check(lib().sdrgpu_polyfir_set_stream(self._h, stream_ptr), "set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_polyfir_get_stream(self._h, ctypes.byref(s)), "get_stream")
-        return s.value or 0
-
-    def output_len(self, n_in: int) -> int:
-        """Outputs per row the next call produces for n_in inputs."""
-        n = ctypes.c_size_t()
-        check(lib().sdrgpu_polyfir_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
-        return n.value
 
     def process(self, x) -> np.ndarray:
         """x: (n,) for nch = 1, else (nch, n) -> (n_out,) or (nch, n_out)."""
@@ -398,9 +284,6 @@ class PolyFir:
                                                ld_out, ctypes.byref(got)),
               "sdrgpu_polyfir_process_dev")
         return got.value
-
-    def sync(self):
-        check(lib().sdrgpu_polyfir_sync(self._h), "sdrgpu_polyfir_sync")
 
 
 def fir_conv_plan(ntaps: int, decim: int = 1, block: int = 0):
@@ -430,7 +313,7 @@ def tuner_word(freq: float, rate: float) -> int:
     return w.value
 
 
-class Tuner:
+class Tuner(TuningWords, Resets, HasOutputLen, Handle):
     """Tuner bank (digital down-converter, sdrgpu_tuner): one wideband stream into K rows, row k
     mixed down by its own frequency, low-passed with the shared real prototype `taps` and
     decimated by `decim`.  Row k is the reference's `signal.filter(c_k).decimate(rate / decim)`
@@ -442,6 +325,8 @@ class Tuner:
     C64, channel-major, the layout Pll, FirBank, Biquad, PolyFir and SampleRateRows read.  State
     (the last len(taps)-1 raw samples, the sample count) carries across blocks; retuning a row
     (set_word / set_freq) has no transient."""
+
+    _family = "tuner"
 
     def __init__(self, taps, decim: int, freqs=None, rate: Optional[float] = None, words=None,
                  sample_kind: int = C64, device: int = 0, _handle=None):
@@ -463,79 +348,16 @@ class Tuner:
         self.sample_kind = sample_kind
         self.device = device
         self.nch = int(w.size)
-        self._h = ctypes.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            if not 0 <= self.decim < 1 << 32:
-                raise _lib.SdrGpuError(_lib.ERR_INVALID, "Tuner: decim out of range")
-            w32 = np.ascontiguousarray(w, dtype=np.uint32)
-            check(lib().sdrgpu_tuner_create(device, sample_kind, self.taps.ctypes.data,
-                                            self.taps.size, self.decim, w32.ctypes.data, w32.size,
-                                            ctypes.byref(self._h)), "sdrgpu_tuner_create")
-
-    def close(self):
-        if self._h:
-            lib().sdrgpu_tuner_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def words(self) -> np.ndarray:
-        """The current tuning words, one uint32 per row."""
-        out = np.empty(self.nch, np.uint32)
-        w = ctypes.c_uint32()
-        for k in range(self.nch):
-            check(lib().sdrgpu_tuner_get_word(self._h, k, ctypes.byref(w)), "sdrgpu_tuner_get_word")
-            out[k] = w.value
-        return out
-
-    @property
-    def freqs(self) -> np.ndarray:
-        """The realised frequencies word * rate / 2^32 in Hz, signed (words at or above 2^31 are
-        negative); in cycles per input sample when no rate was given."""
-        w = self.words.astype(np.int64)
-        w = np.where(w >= 1 << 31, w - (1 << 32), w)
-        return w * (1.0 if self.rate is None else self.rate) / 2.0 ** 32
-
-    def set_word(self, ch: int, word: int):
-        """Retune row ch from the next process call on; the other rows do not change."""
-        if not 0 <= int(word) <= 0xFFFFFFFF or ch < 0:
-            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Tuner.set_word: out of range")
-        check(lib().sdrgpu_tuner_set_word(self._h, ch, int(word)), "sdrgpu_tuner_set_word")
-
-    def set_freq(self, ch: int, freq: float):
-        if self.rate is None:
-            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Tuner.set_freq: the handle has no rate")
-        self.set_word(ch, tuner_word(freq, self.rate))
+        if _handle is None and not 0 <= self.decim < 1 << 32:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Tuner: decim out of range")
+        w32 = np.ascontiguousarray(w, dtype=np.uint32)
+        self._open("create", device, sample_kind, self.taps.ctypes.data, self.taps.size, self.decim,
+                   w32.ctypes.data, w32.size, _handle=_handle)
 
     def clone(self) -> "Tuner":
-        h = ctypes.c_void_p()
-        check(lib().sdrgpu_tuner_clone(self._h, ctypes.byref(h)), "sdrgpu_tuner_clone")
+        h = self._clone_handle()
         return Tuner(self.taps, self.decim, rate=self.rate, words=self.words,
                      sample_kind=self.sample_kind, device=self.device, _handle=h)
-
-    def reset(self):
-        check(lib().sdrgpu_tuner_reset(self._h), "sdrgpu_tuner_reset")
-
-    def set_stream(self, stream_ptr: Optional[int]):
-        check(lib().sdrgpu_tuner_set_stream(self._h, stream_ptr), "sdrgpu_tuner_set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_tuner_get_stream(self._h, ctypes.byref(s)), "sdrgpu_tuner_get_stream")
-        return s.value or 0
-
-    def output_len(self, n_in: int) -> int:
-        """Outputs per row the next process() call produces for n_in inputs."""
-        n = ctypes.c_size_t()
-        check(lib().sdrgpu_tuner_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
-        return n.value
 
     def process(self, x) -> np.ndarray:
         """x: (n,) host samples (CU8: 2n bytes or (n, 2)) -> (K, n_out) complex64."""
@@ -556,9 +378,6 @@ class Tuner:
                                              ctypes.byref(got)), "sdrgpu_tuner_process_dev")
         return got.value
 
-    def sync(self):
-        check(lib().sdrgpu_tuner_sync(self._h), "sdrgpu_tuner_sync")
-
     def upconverter(self, taps) -> "Upconverter":
         """The up-converter bank of this tuner's words, interp = decim, rate and device with the
         prototype `taps`: the way back from its rows."""
@@ -575,7 +394,7 @@ def demod_fm_gain(rate: float, deviation: float) -> float:
     return g.value
 
 
-class Demod:
+class Demod(Resets, HasOutputLen, Handle):
     """Demodulator bank (sdrgpu_demod): a per-sample detector over `nch` channel rows, c64 or
     rtl_tcp CU8 in, f32 out, each operation one f32 IEEE operation:
 
@@ -588,18 +407,15 @@ class Demod:
     stage (its only demodulator is the PLL, pll.rs).  State is the last sample per row and carries
     across blocks, so any partition into blocks gives the same bits; rows are independent."""
 
+    _family = "demod"
+
     def __init__(self, mode: int, gain: float = 1.0, nch: int = 1, sample_kind: int = C64,
                  device: int = 0, _handle=None):
         self.mode = int(mode)
         self.nch = int(nch)
         self.sample_kind = sample_kind
         self.device = device
-        self._h = ctypes.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            check(lib().sdrgpu_demod_create(device, sample_kind, self.mode, float(gain), self.nch,
-                                            ctypes.byref(self._h)), "sdrgpu_demod_create")
+        self._open("create", device, sample_kind, self.mode, float(gain), self.nch, _handle=_handle)
 
     @classmethod
     def fm(cls, rate: float, deviation: float, nch: int = 1, sample_kind: int = C64,
@@ -607,48 +423,18 @@ class Demod:
         """The quadrature FM discriminator at sample rate `rate`, output in units of `deviation`."""
         return cls(_lib.DEMOD_FM, demod_fm_gain(rate, deviation), nch, sample_kind, device)
 
-    def close(self):
-        if self._h:
-            lib().sdrgpu_demod_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     @property
     def gain(self) -> float:
-        g = ctypes.c_float()
-        check(lib().sdrgpu_demod_get_gain(self._h, ctypes.byref(g)), "sdrgpu_demod_get_gain")
-        return g.value
+        return self._get(ctypes.c_float, "get_gain")
 
     def set_gain(self, gain: float):
         """From the next process call on; ordered after the calls enqueued before it."""
-        check(lib().sdrgpu_demod_set_gain(self._h, float(gain)), "sdrgpu_demod_set_gain")
+        self._call("set_gain", float(gain))
 
     def clone(self) -> "Demod":
-        h = ctypes.c_void_p()
-        check(lib().sdrgpu_demod_clone(self._h, ctypes.byref(h)), "sdrgpu_demod_clone")
+        h = self._clone_handle()
         return Demod(self.mode, nch=self.nch, sample_kind=self.sample_kind, device=self.device,
                      _handle=h)
-
-    def reset(self):
-        check(lib().sdrgpu_demod_reset(self._h), "sdrgpu_demod_reset")
-
-    def set_stream(self, stream_ptr: Optional[int]):
-        check(lib().sdrgpu_demod_set_stream(self._h, stream_ptr), "sdrgpu_demod_set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_demod_get_stream(self._h, ctypes.byref(s)), "sdrgpu_demod_get_stream")
-        return s.value or 0
-
-    def output_len(self, n_in: int) -> int:
-        n = ctypes.c_size_t()
-        check(lib().sdrgpu_demod_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
-        return n.value
 
     def process(self, x) -> np.ndarray:
         """x: (n,) for nch = 1, else (nch, n) host samples (CU8: 2n bytes per row, or (.., n, 2))
@@ -677,12 +463,9 @@ class Demod:
               "sdrgpu_demod_process_dev")
         return n
 
-    def sync(self):
-        check(lib().sdrgpu_demod_sync(self._h), "sdrgpu_demod_sync")
-
 
 # ---------------------------------------------------------------------------- Agc
-class Agc:
+class Agc(Resets, HasOutputLen, Handle):
     """AGC bank (sdrgpu_agc): a gain loop over `nch` channel rows, c64 or f32, output of the same
     kind.  The gain moves once per frame of `frame` samples (frames aligned to the stream index),
     each operation one f32 IEEE operation:
@@ -695,6 +478,8 @@ class Agc:
     frame sum, samples counted) carries across blocks, so any partition into blocks gives the same
     bits; rows are independent.  frame = 1 is the classic per-sample loop: correct, but serial."""
 
+    _family = "agc"
+
     FIELDS = ("reference", "attack", "decay", "min_gain", "max_gain", "initial_gain")
 
     def __init__(self, reference: float = 1.0, attack: float = 0.1, decay: float = 0.01,
@@ -704,31 +489,15 @@ class Agc:
         self.frame = int(frame)
         self.sample_kind = sample_kind
         self.device = device
-        self._h = ctypes.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            if not 0 <= self.frame < 2 ** 32:
-                raise _lib.SdrGpuError(_lib.ERR_INVALID, "Agc: frame")
-            d = _lib.AgcDesignC(reference, attack, decay, min_gain, max_gain, initial_gain, self.frame)
-            check(lib().sdrgpu_agc_create(device, sample_kind, ctypes.byref(d), self.nch,
-                                          ctypes.byref(self._h)), "sdrgpu_agc_create")
-
-    def close(self):
-        if self._h:
-            lib().sdrgpu_agc_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        if _handle is None and not 0 <= self.frame < 2 ** 32:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Agc: frame")
+        d = _lib.AgcDesignC(reference, attack, decay, min_gain, max_gain, initial_gain, self.frame)
+        self._open("create", device, sample_kind, ctypes.byref(d), self.nch, _handle=_handle)
 
     @property
     def design(self) -> dict:
         d = _lib.AgcDesignC()
-        check(lib().sdrgpu_agc_get_design(self._h, ctypes.byref(d)), "sdrgpu_agc_get_design")
+        self._call("get_design", ctypes.byref(d))
         out = {k: getattr(d, k) for k in self.FIELDS}
         out["frame"] = d.frame
         return out
@@ -743,42 +512,25 @@ class Agc:
                 raise _lib.SdrGpuError(_lib.ERR_INVALID, f"Agc.set_design: {k}")
         cur.update(fields)
         d = _lib.AgcDesignC(*(cur[k] for k in self.FIELDS), cur["frame"])
-        check(lib().sdrgpu_agc_set_design(self._h, ctypes.byref(d)), "sdrgpu_agc_set_design")
+        self._call("set_design", ctypes.byref(d))
 
     def gains(self) -> np.ndarray:
         """The nch current gains, after everything enqueued on the handle's stream: reference /
         gains()[r] is row r's level."""
         g = np.empty(self.nch, np.float32)
-        check(lib().sdrgpu_agc_get_gains(self._h, g.ctypes.data), "sdrgpu_agc_get_gains")
+        self._call("get_gains", g.ctypes.data)
         return g
 
     def last_plan(self):
         """(form, copied) of the most recent non-empty call: form one of _lib.AGC_SHORT, AGC_LDS,
         AGC_STREAM (-1 before the first call), copied whether the input was copied first."""
         f, c = ctypes.c_int(), ctypes.c_int()
-        check(lib().sdrgpu_agc_last_plan(self._h, ctypes.byref(f), ctypes.byref(c)), "sdrgpu_agc_last_plan")
+        self._call("last_plan", ctypes.byref(f), ctypes.byref(c))
         return f.value, bool(c.value)
 
     def clone(self) -> "Agc":
-        h = ctypes.c_void_p()
-        check(lib().sdrgpu_agc_clone(self._h, ctypes.byref(h)), "sdrgpu_agc_clone")
+        h = self._clone_handle()
         return Agc(frame=self.frame, nch=self.nch, sample_kind=self.sample_kind, device=self.device, _handle=h)
-
-    def reset(self):
-        check(lib().sdrgpu_agc_reset(self._h), "sdrgpu_agc_reset")
-
-    def set_stream(self, stream_ptr: Optional[int]):
-        check(lib().sdrgpu_agc_set_stream(self._h, stream_ptr), "sdrgpu_agc_set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_agc_get_stream(self._h, ctypes.byref(s)), "sdrgpu_agc_get_stream")
-        return s.value or 0
-
-    def output_len(self, n_in: int) -> int:
-        n = ctypes.c_size_t()
-        check(lib().sdrgpu_agc_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
-        return n.value
 
     def process(self, x, want_gain: bool = False):
         """x: (n,) for nch = 1, else (nch, n) host samples -> y of x's shape and kind; with
@@ -812,12 +564,9 @@ class Agc:
               "sdrgpu_agc_process_dev")
         return n
 
-    def sync(self):
-        check(lib().sdrgpu_agc_sync(self._h), "sdrgpu_agc_sync")
-
 
 # ---------------------------------------------------------------------------- Upconverter
-class Upconverter:
+class Upconverter(TuningWords, Resets, HasOutputLen, Handle):
     """Up-converter bank (digital up-converter, sdrgpu_upconv): K rows of c64 frames onto any
     frequencies of one wideband stream, the way back from Tuner.  Row k is zero-stuffed by
     `interp` and filtered with the shared real prototype `taps` (PolyFir(taps, interp, 1);
@@ -827,6 +576,8 @@ class Upconverter:
     `words`, or `freqs` in Hz with `rate`, the wideband (output) rate.  State (the last
     ceil(len(taps)/interp)-1 frames per row, the frame count) carries across blocks; retuning a
     row (set_word / set_freq) has no transient."""
+
+    _family = "upconv"
 
     def __init__(self, taps, interp: int, freqs=None, rate: Optional[float] = None, words=None,
                  device: int = 0, _handle=None):
@@ -848,79 +599,16 @@ class Upconverter:
         self.sample_kind = C64
         self.device = device
         self.nch = int(w.size)
-        self._h = ctypes.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            if not 0 <= self.interp < 1 << 32:
-                raise _lib.SdrGpuError(_lib.ERR_INVALID, "Upconverter: interp out of range")
-            w32 = np.ascontiguousarray(w, dtype=np.uint32)
-            check(lib().sdrgpu_upconv_create(device, C64, self.taps.ctypes.data, self.taps.size,
-                                             self.interp, w32.ctypes.data, w32.size,
-                                             ctypes.byref(self._h)), "sdrgpu_upconv_create")
-
-    def close(self):
-        if self._h:
-            lib().sdrgpu_upconv_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def words(self) -> np.ndarray:
-        """The current tuning words, one uint32 per row."""
-        out = np.empty(self.nch, np.uint32)
-        w = ctypes.c_uint32()
-        for k in range(self.nch):
-            check(lib().sdrgpu_upconv_get_word(self._h, k, ctypes.byref(w)), "sdrgpu_upconv_get_word")
-            out[k] = w.value
-        return out
-
-    @property
-    def freqs(self) -> np.ndarray:
-        """The realised frequencies word * rate / 2^32 in Hz, signed (words at or above 2^31 are
-        negative); in cycles per output sample when no rate was given."""
-        w = self.words.astype(np.int64)
-        w = np.where(w >= 1 << 31, w - (1 << 32), w)
-        return w * (1.0 if self.rate is None else self.rate) / 2.0 ** 32
-
-    def set_word(self, ch: int, word: int):
-        """Retune row ch from the next process call on."""
-        if not 0 <= int(word) <= 0xFFFFFFFF or ch < 0:
-            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Upconverter.set_word: out of range")
-        check(lib().sdrgpu_upconv_set_word(self._h, ch, int(word)), "sdrgpu_upconv_set_word")
-
-    def set_freq(self, ch: int, freq: float):
-        if self.rate is None:
-            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Upconverter.set_freq: the handle has no rate")
-        self.set_word(ch, tuner_word(freq, self.rate))
+        if _handle is None and not 0 <= self.interp < 1 << 32:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Upconverter: interp out of range")
+        w32 = np.ascontiguousarray(w, dtype=np.uint32)
+        self._open("create", device, C64, self.taps.ctypes.data, self.taps.size, self.interp,
+                   w32.ctypes.data, w32.size, _handle=_handle)
 
     def clone(self) -> "Upconverter":
-        h = ctypes.c_void_p()
-        check(lib().sdrgpu_upconv_clone(self._h, ctypes.byref(h)), "sdrgpu_upconv_clone")
+        h = self._clone_handle()
         return Upconverter(self.taps, self.interp, rate=self.rate, words=self.words,
                            device=self.device, _handle=h)
-
-    def reset(self):
-        check(lib().sdrgpu_upconv_reset(self._h), "sdrgpu_upconv_reset")
-
-    def set_stream(self, stream_ptr: Optional[int]):
-        check(lib().sdrgpu_upconv_set_stream(self._h, stream_ptr), "sdrgpu_upconv_set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_upconv_get_stream(self._h, ctypes.byref(s)), "sdrgpu_upconv_get_stream")
-        return s.value or 0
-
-    def output_len(self, n_in: int) -> int:
-        """Samples the next process() call produces for n_in frames per row."""
-        n = ctypes.c_size_t()
-        check(lib().sdrgpu_upconv_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
-        return n.value
 
     def process(self, rows) -> np.ndarray:
         """rows: (K, n) host frames ((n,) for K = 1) -> (n*interp,) complex64."""
@@ -944,12 +632,9 @@ class Upconverter:
                                               ctypes.byref(got)), "sdrgpu_upconv_process_dev")
         return got.value
 
-    def sync(self):
-        check(lib().sdrgpu_upconv_sync(self._h), "sdrgpu_upconv_sync")
-
 
 # ---------------------------------------------------------------------- Channelizer
-class Channelizer:
+class Channelizer(Resets, HasOutputLen, Handle):
     """Polyphase channelizer: one wideband stream into nch channel rows.  Channel k is the
     reference's `signal.filter(c_k).decimate(rate / nch)` with the complex taps
     c_k[n] = taps[n] * exp(+2j*pi*k*(n+1)/nch) (fir.rs:23-32, adapters/mod.rs:30-37): the band
@@ -962,6 +647,8 @@ class Channelizer:
     for its m-th output since the stream start, which centres every channel at baseband at
     oversample times the channel spacing."""
 
+    _family = "chan"
+
     def __init__(self, taps, nch: int, sample_kind: int = C64, device: int = 0,
                  oversample: int = 1, _handle=None):
         taps = np.asarray(taps)
@@ -972,57 +659,21 @@ class Channelizer:
         self.sample_kind = sample_kind
         self.device = device
         self.oversample = oversample
-        self._h = ctypes.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            if not 0 <= oversample < 1 << 32:
-                raise _lib.SdrGpuError(_lib.ERR_INVALID, "Channelizer: oversample out of range")
-            pow2 = nch >= 1 and nch & (nch - 1) == 0
-            name = "sdrgpu_chan_create_os" if pow2 else "sdrgpu_chan_create_any"
-            check(getattr(lib(), name)(device, sample_kind, self.taps.ctypes.data, self.taps.size,
-                                       nch, oversample, ctypes.byref(self._h)), name)
-
-    def close(self):
-        if self._h:
-            lib().sdrgpu_chan_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        if _handle is None and not 0 <= oversample < 1 << 32:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Channelizer: oversample out of range")
+        pow2 = nch >= 1 and nch & (nch - 1) == 0
+        self._open("create_os" if pow2 else "create_any", device, sample_kind, self.taps.ctypes.data,
+                   self.taps.size, nch, oversample, _handle=_handle)
 
     def clone(self) -> "Channelizer":
-        h = ctypes.c_void_p()
-        check(lib().sdrgpu_chan_clone(self._h, ctypes.byref(h)), "sdrgpu_chan_clone")
+        h = self._clone_handle()
         return Channelizer(self.taps, self.nch, self.sample_kind, self.device, self.oversample,
                            _handle=h)
-
-    def reset(self):
-        check(lib().sdrgpu_chan_reset(self._h), "sdrgpu_chan_reset")
-
-    def set_stream(self, stream_ptr: Optional[int]):
-        check(lib().sdrgpu_chan_set_stream(self._h, stream_ptr), "sdrgpu_chan_set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_chan_get_stream(self._h, ctypes.byref(s)), "sdrgpu_chan_get_stream")
-        return s.value or 0
 
     @property
     def decim(self) -> int:
         """Input samples per output frame, nch / oversample."""
-        d = ctypes.c_size_t()
-        check(lib().sdrgpu_chan_get_decim(self._h, ctypes.byref(d)), "sdrgpu_chan_get_decim")
-        return d.value
-
-    def output_len(self, n_in: int) -> int:
-        """Outputs per channel the next process() call produces for n_in inputs."""
-        n = ctypes.c_size_t()
-        check(lib().sdrgpu_chan_output_len(self._h, n_in, ctypes.byref(n)), "output_len")
-        return n.value
+        return self._get(ctypes.c_size_t, "get_decim")
 
     def process(self, x) -> np.ndarray:
         """x: (n,) host samples (CU8: 2n bytes or (n, 2)) -> (nch, n_out) complex64."""
@@ -1043,9 +694,6 @@ class Channelizer:
                                             ctypes.byref(got)), "sdrgpu_chan_process_dev")
         return got.value
 
-    def sync(self):
-        check(lib().sdrgpu_chan_sync(self._h), "sdrgpu_chan_sync")
-
     def synthesizer(self, taps) -> "Synthesizer":
         """The synthesis bank of this channelizer's nch, oversample and device with the
         prototype `taps`: the way back from its rows."""
@@ -1053,7 +701,7 @@ class Channelizer:
 
 
 # ---------------------------------------------------------------------- Synthesizer
-class Synthesizer:
+class Synthesizer(Resets, Handle):
     """Polyphase synthesis bank: nch channel rows back into one wideband stream, the way back
     from Channelizer (no reference counterpart; the definition is in include/sdrgpu.h).  Row k
     is un-rotated by conj(exp(-2j*pi*k*(m+1)/oversample)), zero-stuffed by interp = nch /
@@ -1064,6 +712,8 @@ class Synthesizer:
     counts Channelizer takes), and Channelizer.synthesizer(taps) makes the bank that matches a
     channelizer.  oversample 1, 2 or 4, a divisor of nch; ceil(len(taps) / interp) <= 64.  Rows
     and output are C64."""
+
+    _family = "synth"
 
     @classmethod
     def create_any(cls, taps, nch: int, oversample: int = 1, device: int = 0) -> "Synthesizer":
@@ -1088,54 +738,22 @@ class Synthesizer:
         self.nch = nch
         self.oversample = oversample
         self.device = device
-        self._h = ctypes.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            if not 0 <= oversample < 1 << 32:
-                raise _lib.SdrGpuError(_lib.ERR_INVALID, "Synthesizer: oversample out of range")
-            check(lib().sdrgpu_synth_create(device, self.taps.ctypes.data, self.taps.size, nch,
-                                            oversample, ctypes.byref(self._h)), "sdrgpu_synth_create")
-
-    def close(self):
-        if self._h:
-            lib().sdrgpu_synth_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        if _handle is None and not 0 <= oversample < 1 << 32:
+            raise _lib.SdrGpuError(_lib.ERR_INVALID, "Synthesizer: oversample out of range")
+        self._open("create", device, self.taps.ctypes.data, self.taps.size, nch, oversample, _handle=_handle)
 
     def clone(self) -> "Synthesizer":
-        h = ctypes.c_void_p()
-        check(lib().sdrgpu_synth_clone(self._h, ctypes.byref(h)), "sdrgpu_synth_clone")
+        h = self._clone_handle()
         return Synthesizer(self.taps, self.nch, self.oversample, self.device, _handle=h)
-
-    def reset(self):
-        check(lib().sdrgpu_synth_reset(self._h), "sdrgpu_synth_reset")
-
-    def set_stream(self, stream_ptr: Optional[int]):
-        check(lib().sdrgpu_synth_set_stream(self._h, stream_ptr), "sdrgpu_synth_set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_synth_get_stream(self._h, ctypes.byref(s)), "sdrgpu_synth_get_stream")
-        return s.value or 0
 
     @property
     def interp(self) -> int:
         """Output samples per frame, nch / oversample."""
-        d = ctypes.c_size_t()
-        check(lib().sdrgpu_synth_get_interp(self._h, ctypes.byref(d)), "sdrgpu_synth_get_interp")
-        return d.value
+        return self._get(ctypes.c_size_t, "get_interp")
 
     def output_len(self, n_frames: int) -> int:
         """Samples a process() call of n_frames frames per channel produces: n_frames * interp."""
-        n = ctypes.c_size_t()
-        check(lib().sdrgpu_synth_output_len(self._h, n_frames, ctypes.byref(n)), "output_len")
-        return n.value
+        return self._get(ctypes.c_size_t, "output_len", n_frames)
 
     def process(self, s) -> np.ndarray:
         """s: (nch, n) host channel rows -> (n * interp,) complex64."""
@@ -1158,9 +776,6 @@ class Synthesizer:
         check(lib().sdrgpu_synth_process_dev(self._h, d_in_ptr, ld_in, n_frames, d_out_ptr, out_cap,
                                              ctypes.byref(got)), "sdrgpu_synth_process_dev")
         return got.value
-
-    def sync(self):
-        check(lib().sdrgpu_synth_sync(self._h), "sdrgpu_synth_sync")
 
 
 # --------------------------------------------------------------------------- Biquad
@@ -1221,53 +836,27 @@ Identity = _IdentityType()
 
 
 # ------------------------------------------------------------------------------ PLL
-class Biquad:
+class Biquad(Resets, Handle):
     """nch independent Biquad<C, f32> (biquad.rs:4-56) on the GPU, bit-identical outputs;
     `filter.Identity.design(...)` gives the pass-through (simple.rs:3-19)."""
+
+    _family = "biquad"
 
     def __init__(self, design_c, rate: float, sample_kind: int = F32, nch: int = 1,
                  device: int = 0, _handle=None):
         self.design_c, self.rate, self.sample_kind = design_c, rate, sample_kind
         self.nch, self.device = nch, device
-        self._h = ctypes.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            check(lib().sdrgpu_biquad_create(device, sample_kind, ctypes.byref(design_c), rate,
-                                             nch, ctypes.byref(self._h)), "sdrgpu_biquad_create")
-
-    def close(self):
-        if self._h:
-            lib().sdrgpu_biquad_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open("create", device, sample_kind, ctypes.byref(design_c), rate, nch, _handle=_handle)
 
     def coefs(self) -> np.ndarray:
         c = (ctypes.c_float * 5)()
-        check(lib().sdrgpu_biquad_coefs(self._h, c), "sdrgpu_biquad_coefs")
+        self._call("coefs", c)
         return np.array(c[:], dtype=np.float32)
 
     def clone(self) -> "Biquad":
-        h = ctypes.c_void_p()
-        check(lib().sdrgpu_biquad_clone(self._h, ctypes.byref(h)), "sdrgpu_biquad_clone")
+        h = self._clone_handle()
         return Biquad(self.design_c, self.rate, self.sample_kind, self.nch, self.device,
                       _handle=h)
-
-    def reset(self):
-        check(lib().sdrgpu_biquad_reset(self._h), "sdrgpu_biquad_reset")
-
-    def set_stream(self, stream_ptr: Optional[int]):
-        check(lib().sdrgpu_biquad_set_stream(self._h, stream_ptr), "sdrgpu_biquad_set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_biquad_get_stream(self._h, ctypes.byref(s)), "get_stream")
-        return s.value or 0
 
     def process(self, x) -> np.ndarray:
         """x: (n,) for one channel or (nch, n) -> same shape, filtered."""
@@ -1293,22 +882,17 @@ class Biquad:
     def set_time_parallel(self, seg: int = 0, warm: int = 0):
         """Segments of `seg` samples with `warm` samples of warm-up (0, 0: automatic; seg < 0:
         always serial); outputs identical to the serial recurrence."""
-        check(lib().sdrgpu_biquad_set_time_parallel(self._h, seg, warm), "set_time_parallel")
+        self._call("set_time_parallel", seg, warm)
 
     def time_parallel_plan(self, n: int):
         s, w = ctypes.c_long(), ctypes.c_long()
-        check(lib().sdrgpu_biquad_time_parallel_plan(self._h, n, ctypes.byref(s), ctypes.byref(w)),
-              "time_parallel_plan")
+        self._call("time_parallel_plan", n, ctypes.byref(s), ctypes.byref(w))
         return s.value, w.value
 
     def last_time_parallel(self):
         s, r = ctypes.c_long(), ctypes.c_long()
-        check(lib().sdrgpu_biquad_last_time_parallel(self._h, ctypes.byref(s), ctypes.byref(r)),
-              "last_time_parallel")
+        self._call("last_time_parallel", ctypes.byref(s), ctypes.byref(r))
         return s.value, r.value
-
-    def sync(self):
-        check(lib().sdrgpu_biquad_sync(self._h), "sdrgpu_biquad_sync")
 
 
 class PllDesign:
@@ -1330,48 +914,30 @@ class PllDesign:
         return Pll(self.params(rate), nch, device)
 
 
-class Pll:
+class Pll(Resets, Handle):
     """GPU Pll (pll.rs:12-22, 70-85), one per channel.  process() returns
     (output, locked): output = Some(v) -> v, None -> 0.0 (main.rs:49)."""
+
+    _family = "pll"
 
     def __init__(self, params: _lib.PllParamsC, nch: int = 1, device: int = 0, _handle=None):
         self.params = params
         self.nch = nch
         self.device = device
-        self._h = ctypes.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            check(lib().sdrgpu_pll_create(device, ctypes.byref(params), nch,
-                                          ctypes.byref(self._h)), "sdrgpu_pll_create")
-
-    def close(self):
-        if self._h:
-            lib().sdrgpu_pll_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open("create", device, ctypes.byref(params), nch, _handle=_handle)
 
     def clone(self) -> "Pll":
-        h = ctypes.c_void_p()
-        check(lib().sdrgpu_pll_clone(self._h, ctypes.byref(h)), "sdrgpu_pll_clone")
+        h = self._clone_handle()
         return Pll(self.params, self.nch, self.device, _handle=h)
-
-    def reset(self):
-        check(lib().sdrgpu_pll_reset(self._h), "sdrgpu_pll_reset")
 
     def set_input_kind(self, kind: int):
         """_lib.C64 (default) or _lib.CU8 (raw rtl_tcp I/Q bytes) for process_dev /
         process_async (process / process_u8 set it themselves)."""
-        check(lib().sdrgpu_pll_set_input_kind(self._h, kind), "sdrgpu_pll_set_input_kind")
+        self._call("set_input_kind", kind)
 
     def set_output_mode(self, mode: int):
         """_lib.PLL_OUT_FILTER (Pll::apply's output) or _lib.PLL_OUT_STEREO_DIFF."""
-        check(lib().sdrgpu_pll_set_output_mode(self._h, mode), "sdrgpu_pll_set_output_mode")
+        self._call("set_output_mode", mode)
 
     def stereo(self, v):
         """src/main.rs:56-69 with this PLL as `pllpilot`: real audio v (nch, n) or (n,) ->
@@ -1388,18 +954,17 @@ class Pll:
     def set_time_parallel(self, seg: int = 0, warm: int = 0):
         """Time-parallel blocks (bit-identical results): seg = 0 automatic, < 0 off (one serial
         pass), > 0 a forced segment length; warm = warm-up samples (0: 16384)."""
-        check(lib().sdrgpu_pll_set_time_parallel(self._h, seg, warm), "sdrgpu_pll_set_time_parallel")
+        self._call("set_time_parallel", seg, warm)
 
     def last_time_parallel(self):
         """(segments, segments recomputed) of the most recent block (0, 0 when serial)."""
         a, b = ctypes.c_long(), ctypes.c_long()
-        check(lib().sdrgpu_pll_last_time_parallel(self._h, ctypes.byref(a), ctypes.byref(b)),
-              "sdrgpu_pll_last_time_parallel")
+        self._call("last_time_parallel", ctypes.byref(a), ctypes.byref(b))
         return a.value, b.value
 
     def set_phase_timing(self, on: bool = True):
         """Record events around the three kernels of time-parallel blocks (measurement aid)."""
-        check(lib().sdrgpu_pll_set_phase_timing(self._h, 1 if on else 0), "sdrgpu_pll_set_phase_timing")
+        self._call("set_phase_timing", 1 if on else 0)
 
     def last_phase_ms(self):
         """(pass 1, re-run pass, walk) ms of the most recent block (zeros when serial)."""
@@ -1411,17 +976,11 @@ class Pll:
     def time_parallel_plan(self, n: int):
         """(segment length or 0 for one serial pass, warm-up) for a block of n samples."""
         seg, warm = ctypes.c_long(), ctypes.c_long()
-        check(lib().sdrgpu_pll_time_parallel_plan(self._h, n, ctypes.byref(seg), ctypes.byref(warm)),
-              "sdrgpu_pll_time_parallel_plan")
+        self._call("time_parallel_plan", n, ctypes.byref(seg), ctypes.byref(warm))
         return seg.value, warm.value
 
     def set_stream(self, stream_ptr):
-        check(lib().sdrgpu_pll_set_stream(self._h, stream_ptr), "sdrgpu_pll_set_stream")
-
-    def stream(self) -> int:
-        s = ctypes.c_void_p()
-        check(lib().sdrgpu_pll_get_stream(self._h, ctypes.byref(s)), "sdrgpu_pll_get_stream")
-        return s.value or 0
+        self._call("set_stream", stream_ptr)
 
     def process_u8(self, iq):
         """rtl_tcp bytes: iq (nch, 2n) or (2n,) uint8 interleaved I/Q -> (out, locked)."""
@@ -1432,12 +991,12 @@ class Pll:
         n = iq.shape[1] // 2
         out = np.empty((self.nch, max(n, 1)), dtype=np.float32)
         locked = np.empty((self.nch, max(n, 1)), dtype=np.uint8)
-        check(lib().sdrgpu_pll_set_input_kind(self._h, CU8), "sdrgpu_pll_set_input_kind")
+        self._call("set_input_kind", CU8)
         try:
             check(lib().sdrgpu_pll_process(self._h, iq.ctypes.data, n, n, out.ctypes.data,
                                            locked.ctypes.data, out.shape[1]), "sdrgpu_pll_process")
         finally:
-            check(lib().sdrgpu_pll_set_input_kind(self._h, C64), "sdrgpu_pll_set_input_kind")
+            self._call("set_input_kind", C64)
         out, locked = out[:, :n], locked[:, :n]
         return (out[0], locked[0]) if squeeze else (out, locked)
 
@@ -1476,8 +1035,6 @@ class Pll:
         """Public fields Pll::nphase, Pll::value (pll.rs:20-21)."""
         nph = ctypes.c_float()
         val = (ctypes.c_float * 2)()
-        check(lib().sdrgpu_pll_state(self._h, ch, ctypes.byref(nph), val), "sdrgpu_pll_state")
+        self._call("state", ch, ctypes.byref(nph), val)
         return nph.value, complex(val[0], val[1])
 
-    def sync(self):
-        check(lib().sdrgpu_pll_sync(self._h), "sdrgpu_pll_sync")
