@@ -166,9 +166,11 @@ def test_stft_any_size_streaming(sdr, oracle, n, hop):
 
 
 def test_fft_many_frames_batching(sdr, oracle):
-    """Enough frames that the four-step / Bluestein plans run several scratch batches."""
+    """Many frames in one call.  14400 is a one-frame-per-workgroup tile plan (no scratch: 2400
+    workgroups); 4099 (Bluestein, 256 KiB of scratch per frame: 1024 frames per slab) and 20000 (the
+    mixed-radix four-step, 160,000 bytes per frame: 1677 per slab) run several scratch batches."""
     from sdrgpu.device import DeviceBuffer
-    for n, count in ((14400, 2400), (4099, 4500)):
+    for n, count in ((14400, 2400), (4099, 4500), (20000, 1700)):
         rng = np.random.default_rng(n)
         x = cplx(rng, n * count)
         p = sdr.fft.FftPlan(n)

@@ -213,9 +213,21 @@ __device__ __forceinline__ void st_nt(float2* p, float2 v) {
     __builtin_nontemporal_store(r, reinterpret_cast<f2*>(p));
 }
 
+// v[r] *= tw[(m r) & mask], r = 1..R-1: every power read from the table (rounded once from f64)
+// instead of built from tw[m] by twiddle()'s product tree, which carries tw[m]'s rounding r-fold
+template <int R>
+__device__ __forceinline__ void twiddle_table(float2* v, const float2* __restrict__ tw, int m, int mask) {
+#pragma unroll
+    for (int r = 1; r < R; ++r) v[r] = cmul(v[r], tw[(m * r) & mask]);
+}
+
 // NT: non-temporal hint on the streamed frame loads (pass A) and output stores (pass B), so
 // the stream does not evict the MALL-resident scratch slab
-template <int CB, bool NT>
+// TT: every twiddle a table read (twiddle_table).  Bluestein's inner transforms: two of them make
+// one Bluestein transform, whose error is sqrt(2) times theirs, and with the product trees the
+// 64K plan is the least accurate power-of-two plan (l2 3.6e-7 of RMS against 2.5 - 3.1e-7).  The
+// 15-way gathers cost the streaming STFT its speed (the comment at the launch), so only there.
+template <int CB, bool NT, bool TT = false>
 __global__ __launch_bounds__(16 * CB) void fft64k_pass_a(F64Args a) {
     __shared__ float2 lds[16 * 16 * CB];
     constexpr long M = 65536;
@@ -243,7 +255,10 @@ __global__ __launch_bounds__(16 * CB) void fft64k_pass_a(F64Args a) {
         for (int m = 0; m < 16; ++m) v[m] = frame_sample(s, M, f, 256 * (j + 16 * m) + col);
     }
     Dft<16, false>::run(v);
-    if (j) twiddle<16, false>(v, a.tw, 16 * j);
+    if (j) {
+        if constexpr (TT) twiddle_table<16>(v, a.tw, 16 * j, kTile - 1);
+        else twiddle<16, false>(v, a.tw, 16 * j);
+    }
 #pragma unroll
     for (int ka = 0; ka < 16; ++ka) lds[(ka * 16 + j) * CB + c] = v[ka];
     __syncthreads();
@@ -252,16 +267,21 @@ __global__ __launch_bounds__(16 * CB) void fft64k_pass_a(F64Args a) {
     for (int jj = 0; jj < 16; ++jj) v[jj] = lds[(ka * 16 + jj) * CB + c];
     Dft<16, false>::run(v);
     // v[kb] = column FFT at k1 = ka + 16 kb; x W_65536^{col k1} = W^{col ka} (W_4096^{col})^kb
-    const float2 w1 = a.twM[col * ka];
+    if constexpr (TT) {
 #pragma unroll
-    for (int kb = 0; kb < 16; ++kb) v[kb] = cmul(v[kb], w1);
-    twiddle<16, false>(v, a.tw, col);
+        for (int kb = 0; kb < 16; ++kb) v[kb] = cmul(v[kb], a.twM[col * (ka + 16 * kb)]);  // (col k1 < 65536)
+    } else {
+        const float2 w1 = a.twM[col * ka];
+#pragma unroll
+        for (int kb = 0; kb < 16; ++kb) v[kb] = cmul(v[kb], w1);
+        twiddle<16, false>(v, a.tw, col);
+    }
     float2* S = a.scratch + f * M;
 #pragma unroll
     for (int kb = 0; kb < 16; ++kb) S[(long)(ka + 16 * kb) * 256 + col] = v[kb];
 }
 
-template <int CB, bool NT>
+template <int CB, bool NT, bool TT = false>
 __global__ __launch_bounds__(16 * CB) void fft64k_pass_b(F64Args a) {
     constexpr int P = CB + 1;  // LDS row pitch (float2): conflict-free transposes
     __shared__ float2 lds[256 * P];
@@ -287,7 +307,10 @@ __global__ __launch_bounds__(16 * CB) void fft64k_pass_b(F64Args a) {
     for (int m = 0; m < 16; ++m) v[m] = lds[(j + 16 * m) * P + r];
     __syncthreads();
     Dft<16, false>::run(v);
-    if (j) twiddle<16, false>(v, a.tw, 16 * j);
+    if (j) {
+        if constexpr (TT) twiddle_table<16>(v, a.tw, 16 * j, kTile - 1);
+        else twiddle<16, false>(v, a.tw, 16 * j);
+    }
 #pragma unroll
     for (int ka = 0; ka < 16; ++ka) lds[(ka * 16 + j) * P + r] = v[ka];
     __syncthreads();
@@ -646,6 +669,13 @@ int fft_launch(void* plan, const FftFrames& fr, float2* out, int store_mode, flo
             a.nframes = nf;
             a.out = store_advance(out, f0, p->M, store_mode);
             const dim3 g((unsigned)(nf * (256 / cb))), b(16 * cb);
+            if (store_mode == 2) {  // Bluestein's inner transforms: table twiddles (TT above)
+                hipLaunchKernelGGL((fft64k_pass_a<cb, true, true>), g, b, 0, st, a);
+                SDRGPU_LAUNCH_CHECK();
+                hipLaunchKernelGGL((fft64k_pass_b<cb, true, true>), g, b, 0, st, a);
+                SDRGPU_LAUNCH_CHECK();
+                continue;
+            }
             hipLaunchKernelGGL((fft64k_pass_a<cb, true>), g, b, 0, st, a);
             SDRGPU_LAUNCH_CHECK();
             hipLaunchKernelGGL((fft64k_pass_b<cb, true>), g, b, 0, st, a);
@@ -678,9 +708,9 @@ int fft_launch(void* plan, const FftFrames& fr, float2* out, int store_mode, flo
         const long ga = nf * (a.M1 / (kTile / a.M2));
         const long gb = nf * (a.M2 / (kTile / a.M1));
         const dim3 bA((unsigned)ga), bB((unsigned)gb), b(kFftBlock);
+        // (the DIF path takes 8192 .. 32768 and 65536 has its own: M >= 2^17 here, so M2 >= 256
+        // and M1 >= 512)
         switch (a.M2) {
-        case 64: hipLaunchKernelGGL(fft4_pass_a<64>, bA, b, 0, s, a); break;
-        case 128: hipLaunchKernelGGL(fft4_pass_a<128>, bA, b, 0, s, a); break;
         case 256: hipLaunchKernelGGL(fft4_pass_a<256>, bA, b, 0, s, a); break;
         case 512: hipLaunchKernelGGL(fft4_pass_a<512>, bA, b, 0, s, a); break;
         case 1024: hipLaunchKernelGGL(fft4_pass_a<1024>, bA, b, 0, s, a); break;
@@ -688,8 +718,6 @@ int fft_launch(void* plan, const FftFrames& fr, float2* out, int store_mode, flo
         }
         SDRGPU_LAUNCH_CHECK();
         switch (a.M1) {
-        case 128: hipLaunchKernelGGL(fft4_pass_b<128>, bB, b, 0, s, a); break;
-        case 256: hipLaunchKernelGGL(fft4_pass_b<256>, bB, b, 0, s, a); break;
         case 512: hipLaunchKernelGGL(fft4_pass_b<512>, bB, b, 0, s, a); break;
         case 1024: hipLaunchKernelGGL(fft4_pass_b<1024>, bB, b, 0, s, a); break;
         default: return SDRGPU_ERR_UNSUPPORTED;
