@@ -735,6 +735,119 @@ int sdrgpu_agc_reset(sdrgpu_agc* h);
 int sdrgpu_agc_clone(const sdrgpu_agc* h, sdrgpu_agc** out);
 void sdrgpu_agc_destroy(sdrgpu_agc* h);
 
+/* Squelch bank: a keyed level gate (a side-chain gate) over channel rows: which rows of
+ * sdrgpu_tuner / sdrgpu_chan carry a signal now, and the rest muted.  The level is measured on the
+ * key rows (key_kind: SDRGPU_C64 or SDRGPU_F32), the payload rows (payload_kind: SDRGPU_C64 or
+ * SDRGPU_F32, also the kind of out) are gated; key and payload share the sample index, so the key
+ * can be the c64 station rows in front of sdrgpu_agc and the payload the f32 audio behind
+ * sdrgpu_demod.  The reference has no counterpart; this header is the definition.  One open/closed
+ * decision per row and frame of `frame` samples; it is also the scanner primitive (measure only,
+ * below).
+ * Per-row state is (s, c, q, g_cur, g_prev, last): the open frame's partial sum, the samples
+ * counted in it, the run of consecutive below-frames (a uint32 that saturates at 2^32 - 1), the gate
+ * in force during the open frame, the gate that was in force during the frame before it, and the
+ * level of the last completed frame.  After create or reset s = 0, c = 0, q = 0, g_cur = g_prev =
+ * initial_open, last = 0.  Frames are aligned to the absolute stream index, counted across calls.
+ * With key sample k = (kr, ki) and payload sample x = (xr, xi) at stream index m, j = c before the
+ * increment, and every line one f32 IEEE operation rounded on its own (no FMA contraction):
+ *   p = kr*kr + ki*ki                     SDRGPU_C64: two products, one sum (SDRGPU_DEMOD_POWER, gain 1)
+ *   p = k*k                               SDRGPU_F32
+ *   s = s + p;  c = c + 1                 in stream order
+ *   gate[m] = (float)g_cur                            if g_prev == g_cur
+ *           = (float)(j + 1) / (float)frame           if g_prev == 0, g_cur == 1   (one IEEE division)
+ *           = (float)(frame - 1 - j) / (float)frame   if g_prev == 1, g_cur == 0
+ *             (with ramp == 0, g_prev is taken as equal to g_cur)
+ *   out[m]  = x, bit for bit              in a frame that is open throughout
+ *           = +0 (both parts)             in a frame that is closed throughout, whatever x is
+ *           = (xr*gate, xi*gate)          in a ramping frame (SDRGPU_F32: x*gate)
+ *   if c == frame:
+ *       lvl   = s / (float)frame
+ *       above = lvl >= open_level
+ *       below = !(lvl >= close_level)                 a NaN level counts as below
+ *       q     = below ? min(q + 1, 2^32 - 1) : 0
+ *       o     = above ? 1 : (q > hang ? 0 : g_cur)
+ *       g_prev = g_cur;  g_cur = o;  last = lvl;  s = 0;  c = 0
+ * so a frame is gated by the decisions up to the frame before it: no latency and no look-ahead
+ * (sdrgpu_agc's convention).  A rising ramp reaches exactly 1 at its frame's last sample, a falling
+ * one exactly 0.
+ * Layout: rows as in sdrgpu_agc: row r starts at key + r*ld_key samples of the key's kind, at
+ * in + r*ld_in and out + r*ld_out samples of the payload's kind, at gate + r*ld_gate floats and at
+ * levels + r*ld_frames floats / open + r*ld_frames bytes; the gaps between rows are neither read
+ * nor written (except by the device copy of an overlapped call, below).
+ *   in == NULL    self-keyed: the payload is the key rows; the two kinds must then be equal
+ *                 (SDRGPU_ERR_INVALID otherwise); ld_in is ignored
+ *   out == NULL   measure only, the scanner call: in and gate must be NULL too; only the key is read
+ *   gate          optional: the per-sample gate, f32
+ *   levels, open  optional: lvl and o (0 or 1) of each frame completed in this call, F = (c + n) /
+ *                 frame entries per row; sdrgpu_squelch_frames_len reports F for the next call of
+ *                 n samples; ld_frames < F: SDRGPU_ERR_INVALID with no state touched
+ * The outputs must not overlap each other.
+ * sdrgpu_squelch_set_design replaces every field but frame (its frame field is ignored), keeps the
+ * state, takes effect at the next process call and is ordered after the calls enqueued before it
+ * (the design travels with each call).  sdrgpu_squelch_get_state waits for the handle's stream and
+ * writes last and g_cur of every row; either pointer may be NULL.  reset returns the state to the
+ * one after create; a clone keeps design and state, mid-frame and mid-hang included, and gets its
+ * own stream.  sdrgpu_squelch_level is host only: (float)pow(10, db / 10), computed in double and
+ * rounded once; a non-finite db: SDRGPU_ERR_INVALID.
+ * Partitions: any partition of a stream into calls, n = 0, 1-sample calls and calls that end
+ * mid-frame or mid-hang included, is bit-identical in every output.  Rows: row r of an nch-row handle
+ * is bit-identical to an nch = 1 handle fed row r.  Output length is n.
+ * Non-finite key samples: an infinite sample makes its frame's level +Inf, which is above the open
+ * level; a NaN sample makes it NaN, which counts as below.  Beyond that one decision nothing
+ * changes except through the latch and the run count: the reach of one bad sample is what the
+ * formulas above give, not a bounded window.  Non-finite payload samples reach only their own
+ * output, and only in open or ramping frames.
+ * In place: d_out == d_in with ld_out == ld_in (self-keyed: d_out == d_key with ld_out == ld_key)
+ * runs with no copy, and open frames are then not touched at all.  Every other overlap of an
+ * output with an input runs on a device copy of that input's span and gives the bits of a call on
+ * disjoint buffers.  sdrgpu_squelch_last_plan reports the most recent non-empty call: *form 0 (the
+ * call stayed inside the open frame: no level pass), 1 (frame sums from LDS tiles) or 2 (frame sums
+ * streamed from memory), -1 before the first call; *copied 1 if an input was copied.
+ * Cost: no part of a call is serial in the frames: the state step is two associative scans (a run
+ * count and a latch) over chunks of 64 frames, so n / frame may be as large as the row.  On an
+ * MI355X the state step takes 0.08 ms of a 4.4 ms call on 1024 rows x 2^20 samples
+ * with frame = 256; with millions of frames per row it is still the longest step: 0.31 ms of 0.61
+ * for one row of 2^26 with frame = 64, 2.6 ms of 2.9 for 9 rows x 2^22 with frame = 1 (sdrgpu_agc
+ * takes 54 and 218 ms on those rows).  Closed frames are written as zeros without reading the
+ * payload.
+ * Limits, checked before the device is looked at: a null handle, design or out-pointer, nch == 0,
+ * frame == 0, a kind outside its enum, a non-finite or negative level, close_level > open_level,
+ * ramp or initial_open above 1, hang >= 2^31: SDRGPU_ERR_INVALID; SDRGPU_CU8, frame > 4096 or
+ * nch > 65536: SDRGPU_ERR_UNSUPPORTED.  A pitch below n: SDRGPU_ERR_INVALID with no state touched.
+ * n = 0 is OK and does nothing. */
+typedef struct sdrgpu_squelch sdrgpu_squelch;
+
+typedef struct {
+    float open_level;     /* mean power at or above which a row opens */
+    float close_level;    /* mean power below which a frame counts towards closing, <= open_level */
+    uint32_t hang;        /* below-frames tolerated before closing; 0 closes at the first */
+    uint32_t frame;       /* samples per decision, 1 .. 4096 */
+    uint32_t ramp;        /* 0: switch at frame boundaries; 1: linear ramp over one frame */
+    uint32_t initial_open;/* 0 or 1 */
+} sdrgpu_squelch_design;
+
+int sdrgpu_squelch_level(double db, float* level);
+int sdrgpu_squelch_create(int device, int key_kind, int payload_kind, const sdrgpu_squelch_design* design,
+                          size_t nch, sdrgpu_squelch** out);
+int sdrgpu_squelch_set_design(sdrgpu_squelch* h, const sdrgpu_squelch_design* design);
+int sdrgpu_squelch_get_design(const sdrgpu_squelch* h, sdrgpu_squelch_design* design);
+int sdrgpu_squelch_get_state(const sdrgpu_squelch* h, float* nch_levels, uint8_t* nch_open);
+int sdrgpu_squelch_last_plan(const sdrgpu_squelch* h, int* form, int* copied);
+int sdrgpu_squelch_set_stream(sdrgpu_squelch* h, void* hip_stream);
+int sdrgpu_squelch_get_stream(const sdrgpu_squelch* h, void** hip_stream);
+int sdrgpu_squelch_output_len(const sdrgpu_squelch* h, size_t n_in, size_t* n_out);  /* n_in */
+int sdrgpu_squelch_frames_len(const sdrgpu_squelch* h, size_t n, size_t* frames);
+int sdrgpu_squelch_process(sdrgpu_squelch* h, const void* key, size_t ld_key, const void* in, size_t ld_in,
+                           size_t n, void* out, size_t ld_out, float* gate, size_t ld_gate, float* levels,
+                           uint8_t* open, size_t ld_frames);
+int sdrgpu_squelch_process_dev(sdrgpu_squelch* h, const void* d_key, size_t ld_key, const void* d_in,
+                               size_t ld_in, size_t n, void* d_out, size_t ld_out, float* d_gate,
+                               size_t ld_gate, float* d_levels, uint8_t* d_open, size_t ld_frames);
+int sdrgpu_squelch_sync(sdrgpu_squelch* h);
+int sdrgpu_squelch_reset(sdrgpu_squelch* h);
+int sdrgpu_squelch_clone(const sdrgpu_squelch* h, sdrgpu_squelch** out);
+void sdrgpu_squelch_destroy(sdrgpu_squelch* h);
+
 /* =====================================================================================
  * FFT.
  * Replaces: fft::fft  (src/fft.rs:3-28)  -- forward DFT, fftshift collate, x 1/sqrt(N)

@@ -60,6 +60,11 @@ AGC_SHORT = 0
 AGC_LDS = 1
 AGC_STREAM = 2
 
+# sdrgpu_squelch_last_plan: the AGC's three forms
+SQUELCH_SHORT = 0
+SQUELCH_LDS = 1
+SQUELCH_STREAM = 2
+
 DEBUG_ATAN2F = 0
 DEBUG_SINCOSF = 1
 
@@ -89,6 +94,11 @@ class PllParamsC(ctypes.Structure):
 class AgcDesignC(ctypes.Structure):
     _fields_ = [("reference", c_float), ("attack", c_float), ("decay", c_float), ("min_gain", c_float),
                 ("max_gain", c_float), ("initial_gain", c_float), ("frame", ctypes.c_uint32)]
+
+
+class SquelchDesignC(ctypes.Structure):
+    _fields_ = [("open_level", c_float), ("close_level", c_float), ("hang", ctypes.c_uint32),
+                ("frame", ctypes.c_uint32), ("ramp", ctypes.c_uint32), ("initial_open", ctypes.c_uint32)]
 
 
 class SdrGpuError(RuntimeError):
@@ -268,6 +278,25 @@ SIGNATURES = [
     ("sdrgpu_agc_reset", c_int, [_H]),
     ("sdrgpu_agc_clone", c_int, [_H, _PH]),
     ("sdrgpu_agc_destroy", None, [_H]),
+    # squelch bank
+    ("sdrgpu_squelch_level", c_int, [ctypes.c_double, POINTER(c_float)]),
+    ("sdrgpu_squelch_create", c_int, [c_int, c_int, c_int, POINTER(SquelchDesignC), c_size_t, _PH]),
+    ("sdrgpu_squelch_set_design", c_int, [_H, POINTER(SquelchDesignC)]),
+    ("sdrgpu_squelch_get_design", c_int, [_H, POINTER(SquelchDesignC)]),
+    ("sdrgpu_squelch_get_state", c_int, [_H, c_void_p, c_void_p]),
+    ("sdrgpu_squelch_last_plan", c_int, [_H, POINTER(c_int), POINTER(c_int)]),
+    ("sdrgpu_squelch_set_stream", c_int, [_H, c_void_p]),
+    ("sdrgpu_squelch_get_stream", c_int, [_H, _PH]),
+    ("sdrgpu_squelch_output_len", c_int, [_H, c_size_t, _PS]),
+    ("sdrgpu_squelch_frames_len", c_int, [_H, c_size_t, _PS]),
+    ("sdrgpu_squelch_process", c_int, [_H, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t,
+                                       c_void_p, c_size_t, c_void_p, c_void_p, c_size_t]),
+    ("sdrgpu_squelch_process_dev", c_int, [_H, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t,
+                                           c_void_p, c_size_t, c_void_p, c_void_p, c_size_t]),
+    ("sdrgpu_squelch_sync", c_int, [_H]),
+    ("sdrgpu_squelch_reset", c_int, [_H]),
+    ("sdrgpu_squelch_clone", c_int, [_H, _PH]),
+    ("sdrgpu_squelch_destroy", None, [_H]),
     # FFT
     ("sdrgpu_fft_plan", c_int, [c_int, c_size_t, _PH]),
     ("sdrgpu_fft_set_stream", c_int, [_H, c_void_p]),

@@ -227,6 +227,28 @@ class Signal:
                     yield y
         return Signal(self._rate, gen, sk)
 
+    def squelch(self, open_level: float, close_level: Optional[float] = None, hang: int = 0,
+                frame: int = 256, ramp: bool = True) -> "Signal":
+        """A self-keyed level gate on a c64 or f32 Signal (squelch.Squelch with one row): the same
+        kind and rate, zeros while the mean power of the frames before stays under the levels."""
+        sk = self.sample_kind
+        if sk == _lib.CU8:
+            raise _lib.SdrGpuError(_lib.ERR_UNSUPPORTED, "squelch: CU8 samples")
+        src = self
+
+        def gen():
+            from .squelch import Squelch
+            sq = None
+            for b in src.blocks():
+                b = np.asarray(b).reshape(-1)
+                if sq is None:
+                    kind = sk if sk is not None else (_lib.C64 if np.iscomplexobj(b) else _lib.F32)
+                    sq = Squelch(open_level, close_level, hang, frame, ramp, nch=1, key_kind=kind)
+                y = sq.process(b)
+                if y.size:
+                    yield y
+        return Signal(self._rate, gen, sk)
+
     def resample(self, rate: float) -> "Signal":
         """Signal::resample (src/signal/mod.rs:78-84): SincBestQuality (this library's own
         sinc table)."""
