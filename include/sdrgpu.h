@@ -848,6 +848,91 @@ int sdrgpu_squelch_reset(sdrgpu_squelch* h);
 int sdrgpu_squelch_clone(const sdrgpu_squelch* h, sdrgpu_squelch** out);
 void sdrgpu_squelch_destroy(sdrgpu_squelch* h);
 
+/* Tone bank: T Goertzel detectors over channel rows: is a given tone there?  CTCSS tone squelch on
+ * the audio behind sdrgpu_demod, DTMF, non-coherent FSK on the rows of sdrgpu_chan / sdrgpu_tuner,
+ * a pilot indicator: a few DFT bins at arbitrary frequencies per frame of `frame` = B samples, and
+ * a decision.  The rows are SDRGPU_C64 or SDRGPU_F32.  The reference has no counterpart; this header
+ * is the definition.
+ * Tuning words are sdrgpu_tuner's: theta_t(a) = 2 pi ((w_t a) mod 2^32) / 2^32, and
+ * sdrgpu_tuner_word(freq, rate) makes one.  The T words are shared by all rows and fixed for the
+ * life of the handle.  The table is built once on the host in f64 and rounded once:
+ *   E_t[j] = (er, ei) = (window[j] cos(theta_t(j)), -window[j] sin(theta_t(j))),   j = 0 .. B-1
+ * with window == NULL meaning all ones.
+ * Per-row state is (a_0 .. a_{T-1}, s) plus the handle's sample count: a_t a complex partial sum,
+ * s the partial power, all zero after create or reset.  Frames are aligned to the absolute stream
+ * index, counted across calls.  With x = (xr, xi) at stream index g = f B + j, in stream order and
+ * every line exactly one fmaf (an SDRGPU_F32 row drops the xi lines):
+ *   ar_t = fmaf(xr, er, ar_t);   ar_t = fmaf(-xi, ei, ar_t)
+ *   ai_t = fmaf(xr, ei, ai_t);   ai_t = fmaf(xi, er, ai_t)
+ *   s    = fmaf(xr, xr, s);      s    = fmaf(xi, xi, s)
+ * and at j = B-1, every line one f32 operation with no contraction except where fmaf is written:
+ *   R_t  = exp(-j theta_t(f B))        from the wrapped product w_t ((f B) mod 2^32), f64 sincospi
+ *                                      rounded once
+ *   Z_t  = (fmaf(ar, Rr, -(ai Ri)), fmaf(ar, Ri, ai Rr))
+ *   Y_t  = (Zr / (float)B, Zi / (float)B)                      bins[r T + t][f]
+ *   P_t  = Yr Yr + Yi Yi        (two products, one sum)        power[r T + t][f]
+ *   tot  = s / (float)B                                        total[r][f]
+ *   k    = the lowest t whose P_t no other P_u exceeds (compared with >, so a NaN never wins;
+ *          every P_t NaN: k = 0)
+ *   best = (P_k >= min_power && P_k >= ratio tot) ? k : -1     best[r][f], int32
+ *   a_t = 0;  s = 0
+ * so Y_t[f] = (1/B) sum_j window[j] x[f B + j] exp(-j theta_t(f B + j)): the phase is continuous
+ * across frames and never accumulated.  sdrgpu_tuner with taps = reversed(window) / B and decim = B
+ * computes the same bins of one c64 stream (other rounding).
+ * Outputs, all optional (a call with none still moves the state): bins (c64) and power (f32) are
+ * nch*T rows of F entries, row r*T + t at bins + (r*T + t)*ld_frames; total (f32) and best (int32)
+ * are nch rows of F entries, ld_frames apart.  F is the number of frames completed in the call;
+ * sdrgpu_tones_frames_len (and output_len) reports it for the next call of n samples.  Input row r
+ * starts at in + r*ld_in samples; the gaps between rows are neither read nor written.
+ * set_thresholds takes effect at the next process call and is ordered after the calls enqueued
+ * before it (the thresholds travel with each call).  get_last waits for the handle's stream and
+ * writes best and the T powers of each row's last completed frame (best = -1 and zeros before the
+ * first); either pointer may be NULL.  reset returns the state to the one after create; a clone keeps
+ * the design, the words, the window and the state, mid-frame included, and gets its own stream.
+ * last_plan reports which kernel forms the most recent non-empty call ran, as bits: 1 the VALU form
+ * (a lane per row, frame and tone: the head that completes an open frame, the tail that opens one,
+ * calls inside a frame, short frames and short calls), 2 the 32x32x2 f32 MFMA form, 4 the 16x16x4
+ * one (whole frames); 0 before the first call.
+ * Guarantees.  Any partition of a stream into calls, n = 0, 1-sample calls and calls that end
+ * mid-frame included, is bit-identical in every output; row r of an nch-row handle is bit-identical
+ * to an nch = 1 handle fed row r; tone t of a T-tone handle is bit-identical to a one-tone handle
+ * with w_t; every kernel form gives the same bits (the MFMA's result is the k-ordered fmaf chain).
+ * A non-finite sample reaches the outputs of its own frame of its own row and nothing else.
+ * Limits, checked before the device is looked at: a null handle, design, words or out-pointer,
+ * nch, frame or ntones of 0, a kind outside the enum, a non-finite window entry, a negative or
+ * non-finite min_power or ratio: SDRGPU_ERR_INVALID; SDRGPU_CU8, frame > 4096, ntones > 64 or
+ * nch*ntones > 65536: SDRGPU_ERR_UNSUPPORTED.  ld_in < n, ld_frames < F (with any output given), or
+ * an output that shares bytes with the input or with another output: SDRGPU_ERR_INVALID with no
+ * state touched.  n = 0 is OK and does nothing. */
+typedef struct sdrgpu_tones sdrgpu_tones;
+
+typedef struct {
+    uint32_t frame;   /* B: samples per frame, 1 .. 4096 */
+    uint32_t ntones;  /* T: 1 .. 64 */
+    float min_power;  /* the winner's P must reach this */
+    float ratio;      /* ... and this share of the frame's mean power */
+} sdrgpu_tones_design;
+
+int sdrgpu_tones_create(int device, int kind, const sdrgpu_tones_design* design, const uint32_t* words,
+                        const float* window, size_t nch, sdrgpu_tones** out);
+int sdrgpu_tones_set_thresholds(sdrgpu_tones* h, float min_power, float ratio);
+int sdrgpu_tones_get_design(const sdrgpu_tones* h, sdrgpu_tones_design* design);
+int sdrgpu_tones_get_words(const sdrgpu_tones* h, uint32_t* ntones_words);
+int sdrgpu_tones_get_last(const sdrgpu_tones* h, int32_t* nch_best, float* nch_ntones_power);
+int sdrgpu_tones_last_plan(const sdrgpu_tones* h, int* forms);
+int sdrgpu_tones_set_stream(sdrgpu_tones* h, void* hip_stream);
+int sdrgpu_tones_get_stream(const sdrgpu_tones* h, void** hip_stream);
+int sdrgpu_tones_output_len(const sdrgpu_tones* h, size_t n_in, size_t* n_out);  /* F */
+int sdrgpu_tones_frames_len(const sdrgpu_tones* h, size_t n, size_t* frames);
+int sdrgpu_tones_process(sdrgpu_tones* h, const void* in, size_t ld_in, size_t n, void* bins, float* power,
+                         float* total, int32_t* best, size_t ld_frames);
+int sdrgpu_tones_process_dev(sdrgpu_tones* h, const void* d_in, size_t ld_in, size_t n, void* d_bins,
+                             float* d_power, float* d_total, int32_t* d_best, size_t ld_frames);
+int sdrgpu_tones_sync(sdrgpu_tones* h);
+int sdrgpu_tones_reset(sdrgpu_tones* h);
+int sdrgpu_tones_clone(const sdrgpu_tones* h, sdrgpu_tones** out);
+void sdrgpu_tones_destroy(sdrgpu_tones* h);
+
 /* =====================================================================================
  * FFT.
  * Replaces: fft::fft  (src/fft.rs:3-28)  -- forward DFT, fftshift collate, x 1/sqrt(N)

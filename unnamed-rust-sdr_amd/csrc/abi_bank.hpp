@@ -1,6 +1,6 @@
-// abi_bank.hpp -- what the handles of the eight row banks share (sdrgpu_chan, sdrgpu_synth,
-// sdrgpu_polyfir, sdrgpu_tuner, sdrgpu_upconv, sdrgpu_demod, sdrgpu_agc, sdrgpu_squelch; one
-// abi_*.cpp each).
+// abi_bank.hpp -- what the handles of the nine row banks share (sdrgpu_chan, sdrgpu_synth,
+// sdrgpu_polyfir, sdrgpu_tuner, sdrgpu_upconv, sdrgpu_demod, sdrgpu_agc, sdrgpu_squelch,
+// sdrgpu_tones; one abi_*.cpp each).
 //   RowBank    the device, the stream, the staging buffers, the fixed device allocations, the
 //              ping-pong state pair; open, reset, clone copy, flip, the host-staged call
 //   PolyBank   on top of it, for the two polyphase banks: the bank's shape, the tap image, the

@@ -7,10 +7,11 @@ without the built library raises ImportError.
 """
 from . import _lib
 from ._lib import C64, CU8, F32, SdrGpuError, device_count, lib
-from . import device, fft, filter, resample, rtltcp, shard, signal, squelch  # noqa: F401
+from . import device, fft, filter, resample, rtltcp, shard, signal, squelch, tones  # noqa: F401
 from .filter import Agc, Channelizer, Demod, PolyFir, Synthesizer, Tuner, Upconverter
 from .squelch import Squelch
+from .tones import Tones
 
 lib()  # fail loudly at import if the HIP library is missing
 
-__all__ = ["device", "fft", "filter", "resample", "rtltcp", "shard", "signal", "squelch", "C64", "CU8", "F32", "SdrGpuError", "device_count", "lib", "Agc", "Channelizer", "Demod", "PolyFir", "Squelch", "Synthesizer", "Tuner", "Upconverter"]
+__all__ = ["device", "fft", "filter", "resample", "rtltcp", "shard", "signal", "squelch", "tones", "C64", "CU8", "F32", "SdrGpuError", "device_count", "lib", "Agc", "Channelizer", "Demod", "PolyFir", "Squelch", "Synthesizer", "Tones", "Tuner", "Upconverter"]

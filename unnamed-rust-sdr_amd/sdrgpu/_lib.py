@@ -65,6 +65,11 @@ SQUELCH_SHORT = 0
 SQUELCH_LDS = 1
 SQUELCH_STREAM = 2
 
+# sdrgpu_tones_last_plan: bits, one per kernel form that ran
+TONES_VALU = 1
+TONES_MFMA32 = 2
+TONES_MFMA16 = 4
+
 DEBUG_ATAN2F = 0
 DEBUG_SINCOSF = 1
 
@@ -99,6 +104,11 @@ class AgcDesignC(ctypes.Structure):
 class SquelchDesignC(ctypes.Structure):
     _fields_ = [("open_level", c_float), ("close_level", c_float), ("hang", ctypes.c_uint32),
                 ("frame", ctypes.c_uint32), ("ramp", ctypes.c_uint32), ("initial_open", ctypes.c_uint32)]
+
+
+class TonesDesignC(ctypes.Structure):
+    _fields_ = [("frame", ctypes.c_uint32), ("ntones", ctypes.c_uint32), ("min_power", c_float),
+                ("ratio", c_float)]
 
 
 class SdrGpuError(RuntimeError):
@@ -297,6 +307,25 @@ SIGNATURES = [
     ("sdrgpu_squelch_reset", c_int, [_H]),
     ("sdrgpu_squelch_clone", c_int, [_H, _PH]),
     ("sdrgpu_squelch_destroy", None, [_H]),
+    # tone bank
+    ("sdrgpu_tones_create", c_int, [c_int, c_int, POINTER(TonesDesignC), c_void_p, c_void_p, c_size_t, _PH]),
+    ("sdrgpu_tones_set_thresholds", c_int, [_H, c_float, c_float]),
+    ("sdrgpu_tones_get_design", c_int, [_H, POINTER(TonesDesignC)]),
+    ("sdrgpu_tones_get_words", c_int, [_H, c_void_p]),
+    ("sdrgpu_tones_get_last", c_int, [_H, c_void_p, c_void_p]),
+    ("sdrgpu_tones_last_plan", c_int, [_H, POINTER(c_int)]),
+    ("sdrgpu_tones_set_stream", c_int, [_H, c_void_p]),
+    ("sdrgpu_tones_get_stream", c_int, [_H, _PH]),
+    ("sdrgpu_tones_output_len", c_int, [_H, c_size_t, _PS]),
+    ("sdrgpu_tones_frames_len", c_int, [_H, c_size_t, _PS]),
+    ("sdrgpu_tones_process", c_int, [_H, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_size_t]),
+    ("sdrgpu_tones_process_dev", c_int, [_H, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_size_t]),
+    ("sdrgpu_tones_sync", c_int, [_H]),
+    ("sdrgpu_tones_reset", c_int, [_H]),
+    ("sdrgpu_tones_clone", c_int, [_H, _PH]),
+    ("sdrgpu_tones_destroy", None, [_H]),
     # FFT
     ("sdrgpu_fft_plan", c_int, [c_int, c_size_t, _PH]),
     ("sdrgpu_fft_set_stream", c_int, [_H, c_void_p]),

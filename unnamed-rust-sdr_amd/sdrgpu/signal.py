@@ -249,6 +249,28 @@ class Signal:
                     yield y
         return Signal(self._rate, gen, sk)
 
+    def tones(self, freqs, frame: int, window=None) -> "Signal":
+        """The powers of the tones `freqs` (Hz) per frame of `frame` samples of a c64 or f32 Signal
+        (tones.Tones with one row): blocks of shape (F, len(freqs)), float32, one row per frame, at
+        rate / frame."""
+        sk = self.sample_kind
+        if sk == _lib.CU8:
+            raise _lib.SdrGpuError(_lib.ERR_UNSUPPORTED, "tones: CU8 samples")
+        src = self
+
+        def gen():
+            from .tones import Tones
+            tb = None
+            for b in src.blocks():
+                b = np.asarray(b).reshape(-1)
+                if tb is None:
+                    kind = sk if sk is not None else (_lib.C64 if np.iscomplexobj(b) else _lib.F32)
+                    tb = Tones(freqs, src.rate(), frame, window=window, sample_kind=kind)
+                p = tb.process(b, want=("power",))["power"]
+                if p.shape[-1]:
+                    yield np.ascontiguousarray(p.T)
+        return Signal(self._rate / frame, gen, _lib.F32)
+
     def resample(self, rate: float) -> "Signal":
         """Signal::resample (src/signal/mod.rs:78-84): SincBestQuality (this library's own
         sinc table)."""
